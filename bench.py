@@ -14,7 +14,12 @@ sweeps on the split-half kernel - 22-bit operands, fp32 accumulate, <= 1e-5 (mea
 voxels).  The opt-in `--fast` sweeps (one fp16 plane for the SIGNS of a pass with one consumer + exact values wherever a value is
 read + a statistical certificate: DESIGN.md 3c) are a secondary leg: `config.meshes_per_s_audited_sign_sweeps`.
 
-    python bench.py --gpus N --steps K --warmup W [--grid 256] [--tag nerf3|both9] [--fast]
+    python bench.py --gpus N --steps K --warmup W [--grid 256] [--tag nerf3|both9] [--fast] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` then also writes the arrays the last timed
+step handed its caller (meshes and zoom cube, `DIR/<name>.npy`).  Everything else - the other kind of sweeps, the fp32 MFMA chain, the
+sustained leg, the marching-cubes roofline, the other configurations, the CPU baseline, the comparisons with the reference's runs and
+the side file of the whole record - runs only under `--full`.
 
 Multi-GPU: samples are independent, so ranks share nothing on the data path (weak scaling: K samples per GPU); the
 per-sample records are gathered to rank 0 over RCCL at the end.  One process per GPU.  Either the caller launches the
@@ -401,8 +406,37 @@ def short_line(full, details_path):
         line["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "cpu_model", "physical_cores", "seconds_per_sample",
                                                    "gpu_over_cpu", "sample") if k in cb}
         line["cpu_baseline"]["checked_in_run"] = cb.get("checked_in_run")
-    line["details_file"] = details_path
+    if details_path:
+        line["details_file"] = details_path
     return line
+
+
+DUMP_BYTES = 64_000_000
+
+
+def step_outputs(r, parts):
+    """What the timed path (alignsdf_amd.reconstruct.pipelined_two_pass) hands its caller for one sample: the zoom cube (origin xyz,
+    voxel size) and each part's mesh, vertices in lattice units and faces - empty where marching cubes found no surface."""
+    out = {"zoom_cube": np.array(list(r["origin"]) + [float(r["voxel_size"])], dtype=np.float64)}
+    for p in parts:
+        v, f = r.get("verts_" + p), r.get("faces_" + p)
+        out["verts_" + p] = v.cpu().numpy() if v is not None else np.zeros((0, 3), np.float32)
+        out["faces_" + p] = f.cpu().numpy() if f is not None else np.zeros((0, 3), np.int32)
+    return out
+
+
+def write_outputs(directory, arrays, limit=DUMP_BYTES):
+    """`--dump-outputs`: each array as <directory>/<name>.npy, float32 kept and every other dtype as float64 (exact for the face
+    indices).  Arrays that would exceed `limit` bytes in all are cut to the same share of their rows, picked with a fixed seed, so
+    that two runs with the same arguments stay comparable row for row."""
+    arrays = {k: np.asarray(a, dtype=np.float32 if np.asarray(a).dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        if total > limit and a.ndim > 0 and len(a) > 1:
+            keep = max(1, len(a) * (limit - 4096 * len(arrays)) // total)       # (4 KB per file for the .npy header)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def main():
@@ -416,6 +450,13 @@ def main():
                          "same two shapes with EVERY layer trained on hands grasping objects (tests/golden/train_grasp_decoders.py)")
     ap.add_argument("--branches", default="both", choices=["both", "hand"],
                     help="both = hand + object (2 meshes per sample); hand = HandBranch only (BASELINE configs[0]: 1 mesh per sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg of the record (the other kind of sweeps, the fp32 MFMA chain, the "
+                         "sustained leg, the marching-cubes roofline, the other configurations, the CPU baseline, the comparisons with the "
+                         "reference's runs) and write the side file; the --no-* options and --sustained below select among those legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller (zoom cube, vertices and faces per part) "
+                         "as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-math", action="store_true", help="skip the full record on the fp32 MFMA chain (and its share of parity_in_run)")
     ap.add_argument("--math", default=None, choices=["f32", "f16x3"],
@@ -439,8 +480,11 @@ def main():
                          "it contains the periodic whole-lattice re-calibrations a K-step timed region is too short for; 0 = skip)")
     ap.add_argument("--details", default=None,
                     help="side file for everything that is not in the ONE line (certificates, per-config sweep records, full parity "
-                         "records, the CPU baseline's legs); default gpurun_out/bench_details_<tag>_N<grid>.json")
+                         "records, the CPU baseline's legs); written when this option is given, and by --full at "
+                         "bench_out/bench_details_<tag>_N<grid>.json by default")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no external launcher: one child per GPU, rendezvous on 127.0.0.1
@@ -532,9 +576,12 @@ def main():
 
         def run(self, first, count, n, keep_meshes=False):
             """`count` whole samples through alignsdf_amd.reconstruct.pipelined_two_pass (pass 1 of sample k+1 is queued before the
-            host-synchronous marching cubes of sample k).  One record per sample; the meshes stay on the device."""
+            host-synchronous marching cubes of sample k).  One record per sample; the meshes stay on the device.  `last_result` is
+            what the pipeline yielded for the last sample (--dump-outputs)."""
             out = []
+            self.last_result = None
             for i, r in pipelined_two_pass(self.dec, self.specs, self.stream(first, count), n):
+                self.last_result = r           # (reset above, so a run's samples see the allocator as they would without it)
                 rec = {"i": i, "sample": self.sample_id(i), "origin": tuple(r["origin"]), "voxel_size": float(r["voxel_size"])}
                 for part in self.parts:
                     rec["V_" + part], rec["F_" + part] = r["V_" + part], r["F_" + part]
@@ -594,7 +641,7 @@ def main():
     # the reference's arithmetic class; --fast: the opt-in audited one-plane sweeps)
     # (the meshes of the timed samples are kept only when a later leg compares them vertex for vertex: every kept surface pins its
     # allocator block, the next sample's buffers are then fresh device allocations - 0.3 ms per sample at N = 64, a third of the step)
-    keep = world == 1 and not (args.no_other_math and args.no_other_sweeps)
+    keep = args.full and world == 1 and not (args.no_other_math and args.no_other_sweeps)
     elapsed, k1_ms, done, p1_ms = cfg.timed(args.warmup, args.steps, args.warmup, N, keep_meshes=keep)
     p1_ticks = list(getattr(cfg, "p1_ticks", []))
     # (ordinary sweeps in the timed region: the split-half kernel's own clock stamps, read before any other leg launches it again)
@@ -604,6 +651,9 @@ def main():
     main_coarse, main_fine, main_math = main_sweeps["coarse"], main_sweeps["fine"], dec.math
     records = [dict(index=rank * args.steps + k, V_hand=d["V_hand"], F_hand=d["F_hand"], V_obj=d.get("V_obj", 0), F_obj=d.get("F_obj", 0),
                     milliseconds=0.0) for k, d in enumerate(done)]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(cfg.last_result, parts))
+    cfg.last_result = None
     ranks_report = None
     if world > 1:
         # ---- the first contact with a multi-GPU node verifies itself: every rank contributes the identity of the
@@ -692,7 +742,7 @@ def main():
                 "recalibrations": dec.cert["calibrations"] + dec.cert["fine_calibrations"] - cal0,      # whole-lattice comparisons, either lattice
                 "refused_sweeps": dec.box_stats["fallback"] + dec.band_stats["fallback"] - ref0}
 
-    if world == 1:
+    if world == 1 and args.full:
         from alignsdf_amd import hip_decoder as hd
         audited_main = main_coarse == "box" or main_fine == "band"
         n_sus = args.sustained if args.sustained is not None else (2 * hd.RECAL_EVERY + 2 if N >= 128 else 0)
@@ -949,7 +999,7 @@ def main():
             result["other_configs"] = other_configs
         if sustained is not None:
             result["sustained"] = sustained
-        if world == 1 and not args.no_cpu_baseline and not hand_only:
+        if world == 1 and args.full and not args.no_cpu_baseline and not hand_only:
             # one extra GPU sample (outside every timed region) with its pass-1 volumes kept for the CPU zoom-cube leg
             sid = 0
             lat, mano, obj = cfg.codes[sid]
@@ -963,14 +1013,16 @@ def main():
                 gpu["V_" + part], gpu["F_" + part] = int(v.shape[0]), int(f.shape[0])
             result["cpu_baseline"] = cpu_baseline(args.tag, N, gpu)
             result["cpu_baseline"]["gpu_over_cpu"] = result["value"] / result["cpu_baseline"]["value"]
-        details = args.details or os.path.join(ROOT, "gpurun_out", "bench_details_%s_N%d%s.json" % (args.tag, N, "_hand" if hand_only else ""))
-        try:
-            os.makedirs(os.path.dirname(details), exist_ok=True)
-            with open(details, "w") as f:
-                json.dump(result, f, indent=1)
-        except OSError as e:
-            details = "not written: %s" % e
-        print(json.dumps(short_line(result, os.path.relpath(details, ROOT) if os.path.isabs(details) else details)), flush=True)
+        details = args.details or (os.path.join(ROOT, "bench_out", "bench_details_%s_N%d%s.json" % (args.tag, N, "_hand" if hand_only else ""))
+                                   if args.full else None)
+        if details:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(details)), exist_ok=True)
+                with open(details, "w") as f:
+                    json.dump(result, f, indent=1)
+            except OSError as e:
+                details = "not written: %s" % e
+        print(json.dumps(short_line(result, os.path.relpath(details, ROOT) if details and os.path.isabs(details) else details)), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -1,9 +1,9 @@
 set -x
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/prof_f16; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_under_prof.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline > $O/bench_under_prof.json 2> $O/stats.err
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY" "SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU"; do
   tag=$(echo $set | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/pmc_$tag -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> $O/pmc_$tag.err
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/pmc_$tag -- python bench.py --steps 1 --warmup 0 --full --no-cpu-baseline > /dev/null 2> $O/pmc_$tag.err
 done
 find $O -name "*.csv" | head -40

@@ -4,7 +4,7 @@
 set -x
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/r2/prof; rm -rf $O; mkdir -p $O
-ARGS="--no-cpu-baseline --no-other-math"
+ARGS="--full --no-cpu-baseline --no-other-math"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 6 --warmup 2 $ARGS > $O/bench_under_kernel_trace.json 2> $O/stats.err
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" \

@@ -1,9 +1,9 @@
 # Round-4 profile of bench.py on an MI355X (run through gpurun): kernel-trace stats + PMC passes of the dominant kernel of the
-# default sweeps (sdf_mlp_f16p1_kernel), summarised into gpurun_out/r4/prof/*; copy what should be judged into profiles/ (r04_*).
+# default sweeps (sdf_mlp_f16p1_kernel), summarised into $OUT/r4/prof/* (OUT defaults to bench_out); copy what should be judged into profiles/ (r04_*).
 #   gpurun -- 'bash tools/profile_bench_r4.sh'
 set -x
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
-O=$GRAFT_REPO_ROOT/gpurun_out/r4/prof; rm -rf $O; mkdir -p $O
+O=$PWD/${OUT:-bench_out}/r4/prof; rm -rf $O; mkdir -p $O
 ARGS="--no-cpu-baseline --no-other-math --no-other-sweeps --no-other-configs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 8 --warmup 2 $ARGS > $O/bench_under_kernel_trace.json 2> $O/stats.err
 i=0

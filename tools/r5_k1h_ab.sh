@@ -17,7 +17,7 @@ cp alignsdf_amd/csrc/libalignsdf_hip.so /tmp/lib_keep.so
 for r in 1 2; do
   for v in ${LIBS:-ship r5a}; do
     cp tools/bin/libalignsdf_hip_$v.so alignsdf_amd/csrc/libalignsdf_hip.so
-    python bench.py --coarse exact --fine exact --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --no-other-math --no-other-configs --sustained 0 --details /tmp/k1h_ab_details.json > /dev/null 2>&1
+    python bench.py --coarse exact --fine exact --steps ${STEPS:-8} --warmup 2 --full --no-cpu-baseline --no-other-math --no-other-configs --sustained 0 --details /tmp/k1h_ab_details.json > /dev/null 2>&1
     python -c "
 import json
 d=json.load(open('/tmp/k1h_ab_details.json')); r=d['roofline']; p=d['parity_in_run']

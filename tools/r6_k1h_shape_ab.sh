@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/r6; mkdir -p $O
 for r in 1 2 ${ROUNDS:-3}; do
   for v in 32 16; do
-    ASDF_K1H_SHAPE=$v python bench.py --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --no-other-math --no-other-configs --sustained 0 --details /tmp/ab_details.json > /tmp/ab_line.json 2>/tmp/ab_err.txt || tail -5 /tmp/ab_err.txt
+    ASDF_K1H_SHAPE=$v python bench.py --steps ${STEPS:-8} --warmup 2 --full --no-cpu-baseline --no-other-math --no-other-configs --sustained 0 --details /tmp/ab_details.json > /tmp/ab_line.json 2>/tmp/ab_err.txt || tail -5 /tmp/ab_err.txt
     python - <<PY
 import json
 d = json.loads([l for l in open('/tmp/ab_line.json') if l.startswith('{')][-1]); r = d['roofline']; p = d['config'].get('parity_in_run', {})

@@ -15,7 +15,7 @@ print('DEFAULT N=$1 $2: %d samples %.3f ms/sample = %.2f meshes/s; K1h %.3f ms p
 done
 for cfg in "256 both 1024" "128 both 2048" "64 hand 4096"; do
   set -- $cfg
-  python bench.py --fast --grid $1 --branches $2 --steps 8 --warmup 2 --sustained $3 $ARGS --details gpurun_out/r6/sustained_fast_$1.json 2>/dev/null | tail -1 | python -c "
+  python bench.py --fast --grid $1 --branches $2 --steps 8 --warmup 2 --full --sustained $3 $ARGS --details $(dirname $O)/sustained_fast_$1.json 2>/dev/null | tail -1 | python -c "
 import sys, json
 b = json.loads(sys.stdin.read()); c = b['config']; s = c['sweeps']
 print('--fast  N=$1 $2: %d samples sustained %.3f ms/sample = %.2f meshes/s; whole-lattice comparisons in the leg %d; refused sweeps %d; in the run: %d audited sweeps, %d refused, tail ratios %.2f / %.2f, min tau / estimate %.2f' % (
