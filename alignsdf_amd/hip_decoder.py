@@ -1183,6 +1183,16 @@ class HipSdfDecoder:
         wide = not self.combined and not self.nerf_features and int(self._L.asdf_get_mfma_shape()) == 16
         return "sdf_mlp_f16w_kernel" if wide else "sdf_mlp_f16_kernel"
 
+    def split_half_instance(self, subset=False):
+        """The instantiation behind split_half_kernel, by its kernel symbol: what an ordinary sweep (subset=False) or the voxel-list
+        form of a band sweep / refinement (subset=True) launches - csrc/k1h_kernels.hip k1h_launch / k1h_subset_launch, k1hw_kernels.hip,
+        k1h_nerf_kernels.hip (the CombinedDecoder form carries `combined`, the NeRF-encoded forms `nerf9` / `nerf15`)."""
+        if self.split_half_kernel == "sdf_mlp_f16w_kernel":
+            return "sdf_mlp_f16w_subset_kernel" if subset else "sdf_mlp_f16w_kernel"
+        parts = ["sdf_mlp_f16"] + (["subset"] if subset else []) + (["combined"] if self.combined else [])
+        parts += ["nerf%d" % self.point_feat_size] if self.nerf_features else []
+        return "_".join(parts + ["kernel"])
+
     def sweep_report(self, since=None):
         """Which sweeps produced the volumes behind a run's meshes: one-plane / ordinary / refused-and-repeated counts per pass,
         audits, whole-lattice comparisons, the margins of the statistical certificate, and every mode switch."""

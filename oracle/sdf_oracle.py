@@ -7,30 +7,36 @@ reference lines it follows (paths relative to zerchen/AlignSDF).
 
 Pinning: tests/golden/ref_*.npz hold outputs of the reference itself (imported in the build
 container by tests/golden/make_ref_goldens.py); tests/test_oracle_decoder.py checks this module
-against them bit for bit (grid, zoom cube) or to 1e-6 (decoder outputs).
+against them bit for bit (grid, zoom cube) or to 1e-6 (decoder outputs).  decode_points(..., dtype=torch.float64) runs the
+same chain in fp64: the truth the fp32-class GPU kernels are held to (tests/test_oracle_fp64.py, tests/test_gpu_split_half_fp64.py).
 """
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 
-def effective_weight(weight_v, weight_g):
+def effective_weight(weight_v, weight_g, dtype=None):
     """W = g * v / ||v||_row, exactly what nn.utils.weight_norm's hook computes
-    (networks/model.py:249-250; torch `_weight_norm(v, g, dim=0)`)."""
-    return torch._weight_norm(torch.as_tensor(weight_v), torch.as_tensor(weight_g), 0)
+    (networks/model.py:249-250; torch `_weight_norm(v, g, dim=0)`).  `dtype` (e.g. torch.float64): v and g are cast first, so the
+    fold itself runs in that precision; None = the stored precision."""
+    v, g = torch.as_tensor(weight_v), torch.as_tensor(weight_g)
+    if dtype is not None:
+        v, g = v.to(dtype), g.to(dtype)
+    return torch._weight_norm(v, g, 0)
 
 
-def effective_head_params(state_dict, head):
-    """[(W, b)] * 5 for head 'h' or 'o' from a SeparateDecoder state dict (numpy or torch values)."""
-    out = []
-    for layer in range(5):
-        name = "lin%s%d" % (head, layer)
-        if name + ".weight_v" in state_dict:
-            w = effective_weight(state_dict[name + ".weight_v"], state_dict[name + ".weight_g"])
-        else:
-            w = torch.as_tensor(state_dict[name + ".weight"])
-        out.append((w.float().contiguous(), torch.as_tensor(state_dict[name + ".bias"]).float().contiguous()))
-    return out
+def _layer_params(state_dict, name, dtype):
+    if name + ".weight_v" in state_dict:
+        w = effective_weight(state_dict[name + ".weight_v"], state_dict[name + ".weight_g"],
+                             None if dtype == torch.float32 else dtype)
+    else:
+        w = torch.as_tensor(state_dict[name + ".weight"])
+    return w.to(dtype).contiguous(), torch.as_tensor(state_dict[name + ".bias"]).to(dtype).contiguous()
+
+
+def effective_head_params(state_dict, head, dtype=torch.float32):
+    """[(W, b)] * 5 for head 'h' or 'o' from a SeparateDecoder state dict (numpy or torch values), in `dtype`."""
+    return [_layer_params(state_dict, "lin%s%d" % (head, layer), dtype) for layer in range(5)]
 
 
 def grid_indices(N):
@@ -85,7 +91,7 @@ def kinematic_embedding(xyz, mano_results, point_feat_size, scale_factor, obj_re
     pieces = {}
     if encode_style in ("hand", "both"):
         mano_xyz = wrist + mano_results["rot_center"].reshape(1, 3)   # :387
-        homo = torch.cat([mano_xyz, torch.ones(M, 1)], 1)             # :389-390
+        homo = torch.cat([mano_xyz, torch.ones(M, 1, dtype=xyz.dtype)], 1)   # :389-390
         inv_g = torch.linalg.inv(mano_results["global_trans"].reshape(16, 4, 4))   # :393
         # [16,4,4] @ [M,4,1] -> [M,16,4]
         inv_pts = torch.matmul(inv_g.unsqueeze(0), homo.reshape(M, 1, 4, 1)).squeeze(-1)   # :394-395
@@ -95,7 +101,7 @@ def kinematic_embedding(xyz, mano_results, point_feat_size, scale_factor, obj_re
         hand = torch.cat([mano_xyz.unsqueeze(1), inv_xyz], 1).reshape(M, -1)   # :403-407
         pieces["hand"] = hand * scale_factor / 2                      # :408
     if encode_style in ("obj", "both"):
-        homo_w = torch.cat([wrist, torch.ones(M, 1)], 1)              # :411-412
+        homo_w = torch.cat([wrist, torch.ones(M, 1, dtype=xyz.dtype)], 1)    # :411-412
         inv_o = torch.linalg.inv(obj_results["obj_trans"].reshape(4, 4))   # :414
         o = torch.matmul(inv_o, homo_w.t()).t()                       # :415
         o = o[:, :3] / o[:, 3:4]                                      # :416
@@ -110,7 +116,7 @@ def kinematic_embedding(xyz, mano_results, point_feat_size, scale_factor, obj_re
 def nerf_embedding(xyz, multires):
     """[x, sin(2^k x), cos(2^k x)] (utils/utils.py:433-463,521-533)."""
     outs = [xyz]
-    for freq in 2.0 ** torch.linspace(0.0, multires - 1, steps=multires):
+    for freq in 2.0 ** torch.linspace(0.0, multires - 1, steps=multires, dtype=xyz.dtype):
         outs += [torch.sin(xyz * freq), torch.cos(xyz * freq)]
     return torch.cat(outs, -1)
 
@@ -162,17 +168,9 @@ def combined_decoder(params, inputs):
     return x[:, 0:1], x[:, 1:2]
 
 
-def combined_params(state_dict):
-    """[(W, b)] * 5 of a CombinedDecoder state dict (keys `lin{k}.*`)."""
-    out = []
-    for layer in range(5):
-        name = "lin%d" % layer
-        if name + ".weight_v" in state_dict:
-            w = effective_weight(state_dict[name + ".weight_v"], state_dict[name + ".weight_g"])
-        else:
-            w = torch.as_tensor(state_dict[name + ".weight"])
-        out.append((w.float().contiguous(), torch.as_tensor(state_dict[name + ".bias"]).float().contiguous()))
-    return out
+def combined_params(state_dict, dtype=torch.float32):
+    """[(W, b)] * 5 of a CombinedDecoder state dict (keys `lin{k}.*`), in `dtype`."""
+    return [_layer_params(state_dict, "lin%d" % layer, dtype) for layer in range(5)]
 
 
 def decode_sdf_multi_output(hand_params, obj_params, latent, queries, specs):
@@ -184,15 +182,22 @@ def decode_sdf_multi_output(hand_params, obj_params, latent, queries, specs):
     return separate_decoder(hand_params, obj_params, inputs, latent.shape[1], specs["PointFeatSize"], specs["EncodeStyle"])
 
 
-def decode_points(state_dict, latent, xyz, specs, mano_results=None, obj_results=None, max_batch=2 ** 18):
-    """Chunked decode of explicit points [M,3] -> (hand [M], obj [M]) fp32 tensors."""
+def decode_points(state_dict, latent, xyz, specs, mano_results=None, obj_results=None, max_batch=2 ** 18, dtype=torch.float32):
+    """Chunked decode of explicit points [M,3] -> (hand [M], obj [M]) tensors of `dtype`.
+
+    dtype=torch.float32 (the default) is the reference's arithmetic.  dtype=torch.float64 runs the whole chain in fp64 - the
+    weight-norm fold, the pose inputs (mano_results / obj_results, cast from their stored values), the point embeddings and both
+    decoders - on the same stored weights and inputs: the truth the fp32-class kernels are measured against."""
     if "lin0.bias" in state_dict:
-        hp, op = combined_params(state_dict), None
+        hp, op = combined_params(state_dict, dtype), None
     else:
-        hp, op = effective_head_params(state_dict, "h"), effective_head_params(state_dict, "o")
-    latent = torch.as_tensor(latent).float().reshape(1, -1)
-    xyz = torch.as_tensor(xyz).float()
-    hand, obj = torch.zeros(xyz.shape[0]), torch.zeros(xyz.shape[0])
+        hp, op = effective_head_params(state_dict, "h", dtype), effective_head_params(state_dict, "o", dtype)
+    if dtype != torch.float32:
+        cast = lambda d: None if d is None else {k: torch.as_tensor(v).to(dtype) for k, v in d.items()}
+        mano_results, obj_results = cast(mano_results), cast(obj_results)
+    latent = torch.as_tensor(latent).to(dtype).reshape(1, -1)
+    xyz = torch.as_tensor(xyz).to(dtype)
+    hand, obj = torch.zeros(xyz.shape[0], dtype=dtype), torch.zeros(xyz.shape[0], dtype=dtype)
     with torch.no_grad():
         for head in range(0, xyz.shape[0], max_batch):
             sub = xyz[head:head + max_batch]
