@@ -17,7 +17,7 @@ FEATURES_NERF = 1
 
 ERANGE = -6
 ENOSURF = -7
-ABI_VERSION = 129        # asdf_version() of the library these bindings were written for
+ABI_VERSION = 130        # asdf_version() of the library these bindings were written for
 
 # every symbol include/alignsdf_hip.h declares
 EXPORTS = (
@@ -31,7 +31,7 @@ EXPORTS = (
     "asdf_zoom_cube", "asdf_decode_grid_band_dev", "asdf_decode_grid_dev", "asdf_mc_emit_bounded",
     "asdf_sample_surface_workspace_bytes", "asdf_sample_surface", "asdf_icp_normalise",
     "asdf_decoder_set_sample_host", "asdf_decoder_set_cluster_timeout", "asdf_set_mfma_shape", "asdf_get_mfma_shape",
-    "asdf_debug_pack_host_f16w",
+    "asdf_debug_pack_host_f16w", "asdf_decoder_set_sample_pixel",
 )
 MATH_F32, MATH_F16X3 = 0, 1
 MAX_CLASSES = 8
@@ -88,6 +88,7 @@ def lib():
     L.asdf_decoder_destroy.restype = None
     L.asdf_decoder_set_sample.argtypes = [vp, vp, vp, vp]
     L.asdf_decoder_set_sample_host.argtypes = [vp, vp, vp, vp]
+    L.asdf_decoder_set_sample_pixel.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(f32), ctypes.POINTER(f32), f32, f32, vp]
     L.asdf_decoder_set_cluster_timeout.argtypes = [vp, ctypes.c_uint64]
     L.asdf_set_mfma_shape.argtypes = [ctypes.c_int]
     L.asdf_set_mfma_shape.restype = ctypes.c_int

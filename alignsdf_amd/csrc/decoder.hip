@@ -708,6 +708,14 @@ struct asdf_decoder {
   // the audit of a box sweep runs beside the exact re-evaluation of its candidates (round 5)
   hipStream_t audit_side;
   hipEvent_t ev_audit_fork, ev_audit_join;
+  // pixel-aligned latent (asdf_decoder_set_sample_pixel): bound instead of a latent code until the next asdf_decoder_set_sample*
+  bool pixel_bound;
+  PixelParams pixel;      // the per-sample scalars and the buffers below, as the kernel reads them
+  float* pa_proj;         // [heads][2][H W][512]: P = W_lat . F, grown on demand (32 MiB at 64 x 64)
+  size_t pa_proj_floats;
+  float* pa_cstb;         // [heads][cst floats]: the constants image folded with a zero latent (its c0 / c2 blocks = the biases)
+  float* pa_ws;           // [num_cus][kPixelWsFloats] workspace of the pixel-aligned kernel
+  float* pa_lat;          // [2][kLatent]: the channel mean of F, zeros
 };
 static constexpr int kShortClusters = kClusterCap / kWavePts * kHeads;      // 128
 static constexpr int kNearCap = 1 << 16;      // near-level refinement list of a split-half sweep
@@ -789,7 +797,7 @@ static bool spec_supported(const asdf_decoder_spec_t* s) {
 
 extern "C" {
 
-int asdf_version(void) { return 129; }
+int asdf_version(void) { return 130; }
 
 int asdf_set_mfma_shape(int shape) {
   if (shape != 0 && shape != 16 && shape != 32) return ASDF_EINVAL;
@@ -826,7 +834,8 @@ int asdf_device_count(void) {
 
 void asdf_decoder_destroy(asdf_decoder_t* d) {
   if (!d) return;
-  float* bufs[] = {d->stream, d->wlat, d->wpt, d->bias02, d->cst, d->embed, d->cls, d->stream16, d->cst16, d->stream16_hi, d->a16, d->cst16p1};
+  float* bufs[] = {d->stream, d->wlat, d->wpt, d->bias02, d->cst, d->embed, d->cls, d->stream16, d->cst16, d->stream16_hi, d->a16, d->cst16p1,
+                   d->pa_proj, d->pa_cstb, d->pa_ws, d->pa_lat};
   if (d->side) { (void)hipStreamSynchronize(d->side); (void)hipStreamDestroy(d->side); }
   if (d->audit_side) { (void)hipStreamSynchronize(d->audit_side); (void)hipStreamDestroy(d->audit_side); }
   if (d->ev_audit_fork) (void)hipEventDestroy(d->ev_audit_fork);
@@ -932,6 +941,7 @@ int asdf_decoder_create(const asdf_decoder_spec_t* spec, const asdf_head_params_
   }
   if (e == hipSuccess) e = k1_prepare();
   if (e == hipSuccess) e = k1_cls_prepare();
+  if (e == hipSuccess) e = k1pa_prepare();
   if (e == hipSuccess) e = hipMalloc((void**)&d->latent_stage, kLatent * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&d->status, 16 * sizeof(int));
   if (e == hipSuccess) e = hipMemset(d->status, 0, 16 * sizeof(int));
@@ -1025,6 +1035,7 @@ static int set_sample_fold(asdf_decoder_t* d, const float* latent_dev, hipStream
 int asdf_decoder_set_sample(asdf_decoder_t* d, const float* latent_dev, const float* embed_host, void* stream) {
   if (!d || !latent_dev) return ASDF_EINVAL;
   if (embed_host && d->spec.feature_mode != ASDF_FEATURES_AFFINE) return ASDF_EINVAL;
+  d->pixel_bound = false;
   hipStream_t st = (hipStream_t)stream;
   if (embed_host) {
     ASDF_HIP(hipMemcpyAsync(d->embed, embed_host, sizeof(float) * kHeads * ASDF_MAX_POINT_FEATS * 4,
@@ -1036,6 +1047,7 @@ int asdf_decoder_set_sample(asdf_decoder_t* d, const float* latent_dev, const fl
 int asdf_decoder_set_sample_host(asdf_decoder_t* d, const float* latent_pinned, const float* embed_pinned, void* stream) {
   if (!d || !latent_pinned || !d->latent_stage) return ASDF_EINVAL;
   if (embed_pinned && d->spec.feature_mode != ASDF_FEATURES_AFFINE) return ASDF_EINVAL;
+  d->pixel_bound = false;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(stage_sample_kernel, dim3(1), dim3(256), 0, st, latent_pinned, embed_pinned, d->latent_stage, d->embed,
                      kHeads * ASDF_MAX_POINT_FEATS * 4);
@@ -1069,6 +1081,122 @@ static int set_sample_fold(asdf_decoder_t* d, const float* latent_dev, hipStream
   if (images == 3 && d->a16) hipLaunchKernelGGL(fold_points_f16_kernel, dim3(d->spec.num_heads * 2), dim3(512), 0, st, d->cst16p1, d->a16, d->status);
   ASDF_HIP(hipGetLastError());
   d->sample_bound = true;
+  return ASDF_OK;
+}
+
+namespace asdf {
+// ---- pixel-aligned latent (PixelAlign, utils/utils.py:536-566) ----------------------------------------------------------------
+// channel mean in the reference's order, F.mean(3).mean(2): per channel (one workgroup of 64) the mean of every row over W, then
+// the mean of those over H (fp32 sums; the row sums sequential, the row means in a fixed shuffle tree)
+__global__ __launch_bounds__(64) void channel_mean_kernel(const float* __restrict__ feat, int H, int W, float* __restrict__ mean) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  const float* f = feat + (size_t)c * H * W;
+  float acc = 0.0f;
+  for (int h = lane; h < H; h += 64) {
+    float rs = 0.0f;
+    for (int w = 0; w < W; ++w) rs = __fadd_rn(rs, f[(size_t)h * W + w]);
+    acc = __fadd_rn(acc, __fdiv_rn(rs, (float)W));
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc = __fadd_rn(acc, __shfl_xor(acc, m));
+  if (lane == 0) mean[c] = __fdiv_rn(acc, (float)H);
+}
+
+// P[head][layer][pixel][512 in [tile][half][r] order] = W_lat(head, layer) [512 x 256] . F [256 x H W]: fp32 FMA chains over the
+// 256 channels in order.  64 x 64 output blocks, 256 threads of 4 x 4 outputs, K staged through LDS 16 channels at a time.
+__global__ __launch_bounds__(256) void pixel_project_kernel(const float* __restrict__ wlat, const float* __restrict__ feat, int HW,
+                                                            float* __restrict__ proj) {
+  __shared__ float As[16][64 + 4];
+  __shared__ float Bs[16][64];
+  const int hl = blockIdx.z, row0 = blockIdx.y * 64, pix0 = blockIdx.x * 64;
+  const float* Wm = wlat + (size_t)hl * kHidden * kLatent;
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  float acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0f;
+  for (int k0 = 0; k0 < kLatent; k0 += 16) {
+    for (int e = threadIdx.x; e < 1024; e += 256) {
+      const int r = e >> 4, k = e & 15;
+      As[k][r] = Wm[(size_t)(row0 + r) * kLatent + k0 + k];
+      const int kb = e >> 6, px = e & 63;
+      Bs[kb][px] = pix0 + px < HW ? feat[(size_t)(k0 + kb) * HW + pix0 + px] : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      float a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { a[i] = As[k][ty * 4 + i]; b[i] = Bs[k][tx * 4 + i]; }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int o = row0 + ty * 4 + i, t = o >> 5, rr = o & 31;
+    const int slot = (t * 2 + ((rr >> 2) & 1)) * 16 + (rr & 3) + 4 * (rr >> 3);      // sdf_layout.h: bias arrays [tile][half][r]
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int pp = pix0 + tx * 4 + j;
+      if (pp < HW) proj[((size_t)hl * HW + pp) * kHidden + slot] = acc[i][j];
+    }
+  }
+}
+}  // namespace asdf
+
+int asdf_decoder_set_sample_pixel(asdf_decoder_t* d, const float* feat_dev, int32_t C, int32_t H, int32_t W, const float cam3x4[12],
+                                  const float root3[3], float image_size, float scale_factor, void* stream) {
+  if (!d || !feat_dev || !cam3x4 || !root3) return ASDF_EINVAL;
+  if (C != d->spec.latent_size || H < 1 || H > 256 || W < 1 || W > 256) return ASDF_EINVAL;
+  if (!(image_size > 0.0f) || !(scale_factor > 0.0f)) return ASDF_EINVAL;
+  // SeparateDecoder with xyz point features only (the PA form of the fp32 chain: k1pa_kernels.hip)
+  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->spec.point_feats[0] != 3 ||
+      d->spec.point_feats[1] != 3)
+    return ASDF_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const CstOffsets co = cst_offsets(2);
+  const size_t hw = (size_t)H * W, need = (size_t)kHeads * 2 * hw * kHidden;
+  if (need > d->pa_proj_floats) {
+    if (d->pa_proj) { ASDF_HIP(hipStreamSynchronize(st)); ASDF_HIP(hipFree(d->pa_proj)); d->pa_proj = nullptr; d->pa_proj_floats = 0; }
+    ASDF_HIP(hipMalloc((void**)&d->pa_proj, need * sizeof(float)));
+    d->pa_proj_floats = need;
+  }
+  if (!d->pa_cstb) {
+    ASDF_HIP(hipMalloc((void**)&d->pa_cstb, (size_t)kHeads * co.floats * sizeof(float)));
+    ASDF_HIP(hipMemcpy(d->pa_cstb, d->cst, (size_t)kHeads * co.floats * sizeof(float), hipMemcpyDeviceToDevice));
+    ASDF_HIP(hipMalloc((void**)&d->pa_ws, (size_t)d->num_cus * kPixelWsFloats * sizeof(float)));
+    ASDF_HIP(hipMalloc((void**)&d->pa_lat, 2 * kLatent * sizeof(float)));
+    ASDF_HIP(hipMemset(d->pa_lat, 0, 2 * kLatent * sizeof(float)));
+  }
+  // outside the image: the ordinary fold (K0) of the channel mean, into every constants image as asdf_decoder_set_sample does
+  hipLaunchKernelGGL(channel_mean_kernel, dim3(C), dim3(64), 0, st, feat_dev, H, W, d->pa_lat);
+  ASDF_HIP(hipGetLastError());
+  { const int rc = set_sample_fold(d, d->pa_lat, st); if (rc != ASDF_OK) return rc; }
+  // inside: the biases (the same fold with a zero latent) and P = W_lat . F of both heads and both latent-carrying layers
+  FoldParams fp;
+  std::memset(&fp, 0, sizeof(fp));
+  fp.wlat = d->wlat; fp.wpt = d->wpt; fp.bias02 = d->bias02; fp.embed = d->embed; fp.latent = d->pa_lat + kLatent;
+  fp.kp = d->kp;
+  fp.cst[0] = d->pa_cstb;
+  for (int h = 0; h < kHeads; ++h) {
+    fp.pf[h] = d->spec.point_feats[h];
+    for (int i = 0; i < 3; ++i) { fp.s2[i][h] = 1.0f; fp.s0[i][h] = 1.0f; }
+  }
+  hipLaunchKernelGGL(fold_sample_kernel, dim3(kHeads * 2 * kHidden / 4, 1), dim3(256), 0, st, fp);
+  hipLaunchKernelGGL(pixel_project_kernel, dim3((unsigned)((hw + 63) / 64), kHidden / 64, kHeads * 2), dim3(256), 0, st, d->wlat, feat_dev,
+                     (int)hw, d->pa_proj);
+  ASDF_HIP(hipGetLastError());
+  PixelParams& q = d->pixel;
+  q.proj = d->pa_proj; q.cstb = d->pa_cstb; q.ws = d->pa_ws;
+  for (int i = 0; i < 12; ++i) q.cam[i] = cam3x4[i];
+  for (int i = 0; i < 3; ++i) q.root[i] = root3[i];
+  q.image_size = image_size; q.scale = scale_factor; q.H = H; q.W = W;
+  d->pixel_bound = true;
   return ASDF_OK;
 }
 
@@ -1124,6 +1252,8 @@ static int launch_decode(asdf_decoder_t* d, DecodeParams& p, hipStream_t st) {
     ASDF_HIP(hipGetLastError());
   }
   const bool want_cls = p.logits || p.labels;
+  // a pixel-aligned sample: the fp32 chain's PA form only (lattice sweeps and point lists; no label pass, no voxel lists)
+  if (d->pixel_bound && (want_cls || d->math != ASDF_MATH_F32 || p.mode == kGridSubset || two_out)) return ASDF_EINVAL;
   if (!two_out) {
     if (!p.sdf0 && !p.sdf1 && !want_cls) return ASDF_OK;
     if (!p.sdf1) p.num_mlps = 1;
@@ -1185,7 +1315,8 @@ static int launch_decode(asdf_decoder_t* d, DecodeParams& p, hipStream_t st) {
     }
   } else {
     if (d->ev_start) ASDF_HIP(hipEventRecord((hipEvent_t)d->ev_start, st));
-    k1_launch(d->kp, two_out, p, grid, st);
+    if (d->pixel_bound) k1pa_launch(p, d->pixel, grid, st);
+    else k1_launch(d->kp, two_out, p, grid, st);
     if (d->ev_stop) ASDF_HIP(hipEventRecord((hipEvent_t)d->ev_stop, st));
     d->ev_start = d->ev_stop = nullptr;
   }
@@ -1309,7 +1440,7 @@ int asdf_decode_grid_box(asdf_decoder_t* d, int32_t N, const float origin[3], fl
                          float* scratch_hand_dev, float* scratch_obj_dev, int32_t* bbox_dev, void* stream) {
   if (!d || !origin || !bbox_dev || N < 2 || N > 1024 || !(tau > 0.0f) || !(tau < 0.5f)) return ASDF_EINVAL;
   if (grid_mode != ASDF_GRID_REFERENCE && grid_mode != ASDF_GRID_INTEGER) return ASDF_EINVAL;
-  if (!d->stream16_hi || !d->sample_bound || !d->p1_usable) return ASDF_EINVAL;
+  if (!d->stream16_hi || !d->sample_bound || !d->p1_usable || d->pixel_bound) return ASDF_EINVAL;
   const bool two_out = d->spec.num_heads == 1;
   if (two_out ? !(scratch_hand_dev && scratch_obj_dev) : !(scratch_hand_dev || scratch_obj_dev)) return ASDF_EINVAL;
   hipStream_t st = (hipStream_t)stream;
@@ -1427,7 +1558,7 @@ static int decode_grid_band_impl(asdf_decoder_t* d, int32_t N, const float* orig
                                  int32_t grid_mode, float tau, float* sdf_hand_dev, float* sdf_obj_dev, int32_t* rec_dev, void* stream) {
   if (!d || (!origin && !lattice_dev) || !rec_dev || N < 2 || N > 1024 || !(tau > 0.0f) || !(tau < 0.5f)) return ASDF_EINVAL;
   if (grid_mode != ASDF_GRID_REFERENCE && grid_mode != ASDF_GRID_INTEGER) return ASDF_EINVAL;
-  if (!d->stream16_hi || !d->sample_bound || !d->p1_usable) return ASDF_EINVAL;
+  if (!d->stream16_hi || !d->sample_bound || !d->p1_usable || d->pixel_bound) return ASDF_EINVAL;
   const bool two_out = d->spec.num_heads == 1;       // CombinedDecoder: one MLP, both columns from every evaluation
   if (two_out ? !(sdf_hand_dev && sdf_obj_dev) : (!sdf_hand_dev && !sdf_obj_dev)) return ASDF_EINVAL;
   hipStream_t st = (hipStream_t)stream;
@@ -1570,7 +1701,7 @@ int asdf_decode_points(asdf_decoder_t* d, const float* xyz_dev, int64_t M, float
 
 int asdf_decoder_set_math(asdf_decoder_t* d, int32_t math) {
   if (!d || (math != ASDF_MATH_F32 && math != ASDF_MATH_F16X3)) return ASDF_EINVAL;
-  if (math == ASDF_MATH_F16X3 && !d->stream16) return ASDF_EINVAL;
+  if (math == ASDF_MATH_F16X3 && (!d->stream16 || d->pixel_bound)) return ASDF_EINVAL;
   d->math = math;
   return ASDF_OK;
 }

@@ -37,6 +37,9 @@ void k1_launch(int kp, bool two_out, const DecodeParams& p, int grid, hipStream_
 // waves - or, for the shortest lists, four workgroups per block (sdf_mlp_short_kernel.h); returns at once for lists longer than p.short_max
 void k1_short_launch(bool two_out, const DecodeParams& p, const ShortParams& sp, hipStream_t st);
 void k1_cls_launch(int kp, bool two_out, const DecodeParams& p, int grid, hipStream_t st);
+// the fp32 chain with a pixel-aligned latent (k1pa_kernels.hip): SeparateDecoder, xyz features, lattice sweeps and point lists
+hipError_t k1pa_prepare();
+void k1pa_launch(const DecodeParams& p, const PixelParams& px, int grid, hipStream_t st);
 void k1h_launch(int kp, bool two_out, const DecodeParams& p, int grid, hipStream_t st);
 // the W form (16x16x32 MFMAs) of the SeparateDecoder kernels with affine point features: k1hw_kernels.hip
 hipError_t k1hw_prepare();

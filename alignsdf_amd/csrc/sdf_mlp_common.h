@@ -95,6 +95,22 @@ struct DecodeParams {
   int num_class;
 };
 
+// Pixel-aligned latent (PixelAlign, utils/utils.py:536-566): the per-sample inputs of the K1 form whose layer-0 / layer-2 accumulators
+// start from a bicubic gather of projected feature maps (sdf_mlp_kernel.h: PA, k1pa_kernels.hip).  A kernel argument of its own
+// beside DecodeParams: a larger DecodeParams would move the hidden kernel arguments of every other decoder kernel.
+struct PixelParams {
+  const float* proj;        // [heads][layer 0 / 2][H * W][512 in [tile][half][r] order]: P = W_lat . F per pixel (asdf_decoder_set_sample_pixel)
+  const float* cstb;        // [heads][CstLayout<2>::kFloats]: the constants image folded with a ZERO latent - its c0 / c2 blocks are the
+                            // biases b (+ the point-feature column 3) that an in-image point adds to its gather
+  float cam[12];            // cam_intr [3][4]
+  float root[3];            // mano_results["joints"][0][0]: camera-space position of the wrist frame's origin
+  float image_size;         // specs["ImageSize"][0]
+  float scale;              // specs["SdfScaleFactor"]
+  int H, W;                 // feature map size, 1 .. 256 each
+  float* ws;                // [grid][kPixelWsFloats]: the gathered layer-0 / layer-2 accumulators of a workgroup's current tile
+};
+constexpr int kPixelWsFloats = kWaves * 2 * kTilesHidden * 4 * 64 * 4;      // 512 KiB per workgroup (sdf_mlp_kernel.h: pixel_prologue)
+
 __device__ __forceinline__ void lds_dma16(const float* gsrc, unsigned lds_dst) {
   unsigned keep;
   asm volatile(

@@ -76,6 +76,129 @@ __device__ __forceinline__ float nerf_feature(int f, float x0, float x1, float x
   return r < 3 ? sinf(arg) : cosf(arg);
 }
 
+// ---- pixel-aligned latent (PA): the latent of a point is a bicubic sample of the feature map F [256][H][W] at the point's
+// projection, or F's channel mean outside the image (utils/utils.py:536-558).  grid_sample is linear in F, so the latent columns of
+// layer l reach the accumulator as  b + sum_taps w_t(uv) P_l[:, tap]  with P_l = W_lat(l) . F per pixel (asdf_decoder_set_sample_pixel);
+// outside the image it is the ordinary fold of the mean (the constants block).  Only the accumulator initialisation changes.
+struct PixelTaps {
+  bool in;                  // the point projects into the image (inclusive -1 <= u, v <= 1; NaN / inf from z = 0 are outside)
+  float wx[4], wy[4];       // bicubic weights of the tap columns / rows (0 for taps outside the map: zero padding)
+  int col[4], row[4];       // tap column / row * W, clamped into the map
+};
+
+// projection op for op as pixel_alignment (utils/utils.py:538-546; this unit is built with -ffp-contract=off): xyz * 2 / scale + root,
+// cam [3x4] . (x, y, z, 1), xy / z, / ImageSize * 2 - 1.  Weights as torch grid_sample(mode="bicubic", align_corners=True,
+// padding_mode="zeros"): ix = (u + 1) / 2 (W - 1), taps floor(ix) - 1 .. + 2, cubic convolution with A = -0.75.
+__device__ __forceinline__ PixelTaps pixel_taps(const PixelParams& q, float x0, float x1, float x2) {
+  const float c0 = __fadd_rn(__fdiv_rn(__fmul_rn(x0, 2.0f), q.scale), q.root[0]);
+  const float c1 = __fadd_rn(__fdiv_rn(__fmul_rn(x1, 2.0f), q.scale), q.root[1]);
+  const float c2 = __fadd_rn(__fdiv_rn(__fmul_rn(x2, 2.0f), q.scale), q.root[2]);
+  float h[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    h[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(q.cam[4 * i], c0), __fmul_rn(q.cam[4 * i + 1], c1)), __fmul_rn(q.cam[4 * i + 2], c2)),
+                     q.cam[4 * i + 3]);
+  const float u = __fsub_rn(__fmul_rn(__fdiv_rn(__fdiv_rn(h[0], h[2]), q.image_size), 2.0f), 1.0f);
+  const float v = __fsub_rn(__fmul_rn(__fdiv_rn(__fdiv_rn(h[1], h[2]), q.image_size), 2.0f), 1.0f);
+  PixelTaps t;
+  t.in = u >= -1.0f && u <= 1.0f && v >= -1.0f && v <= 1.0f;
+  // (an outside point never reads its taps: finite placeholders keep the float -> int conversions defined)
+  const float ix = t.in ? __fmul_rn(__fdiv_rn(__fadd_rn(u, 1.0f), 2.0f), (float)(q.W - 1)) : 0.0f;
+  const float iy = t.in ? __fmul_rn(__fdiv_rn(__fadd_rn(v, 1.0f), 2.0f), (float)(q.H - 1)) : 0.0f;
+  const float fx = floorf(ix), fy = floorf(iy);
+  auto coeffs = [](float tt, float (&c)[4]) {
+    const float A = -0.75f;
+    auto far = [&](float x) { return __fsub_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fsub_rn(__fmul_rn(A, x), -3.75f), x), -6.0f), x), -3.0f); };
+    auto near = [&](float x) { return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(1.25f, x), 2.25f), x), x), 1.0f); };
+    c[0] = far(__fadd_rn(tt, 1.0f));
+    c[1] = near(tt);
+    c[2] = near(__fsub_rn(1.0f, tt));
+    c[3] = far(__fsub_rn(2.0f, tt));
+  };
+  float cx[4], cy[4];
+  coeffs(__fsub_rn(ix, fx), cx);
+  coeffs(__fsub_rn(iy, fy), cy);
+  const int x0i = (int)fx - 1, y0i = (int)fy - 1;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int xj = x0i + j, yj = y0i + j;
+    t.wx[j] = xj >= 0 && xj < q.W ? cx[j] : 0.0f;
+    t.wy[j] = yj >= 0 && yj < q.H ? cy[j] : 0.0f;
+    t.col[j] = min(max(xj, 0), q.W - 1);
+    t.row[j] = min(max(yj, 0), q.H - 1) * q.W;
+  }
+  return t;
+}
+
+// The gathered accumulators are computed in front of layer 0, where nothing else is live, and parked in a per-workgroup workspace
+// (PixelParams::ws; layers 0 and 2 then load them as they load a bias block): inside layer 2 the MLP's register budget has no room for
+// a gather in flight.  Workspace order [wave][layer * 16 + tile][float4 c][lane 0..63][4]: one (layer, tile) of a wave is 4 KiB, a
+// lane's four float4 lie at immediate offsets 0 / 1 / 2 / 3 KiB of one address.
+// (kPixelWsFloats, sdf_mlp_common.h, = 512 KiB per workgroup)
+
+// this wave's part of its workgroup's workspace
+__device__ __forceinline__ float* pixel_ws(const PixelParams& q, int wave) {
+  return q.ws + (size_t)blockIdx.x * kPixelWsFloats + (size_t)wave * (kPixelWsFloats / kWaves);
+}
+
+// (the uniform base is made opaque at every use: hoisted, the 32 per-tile addresses of a lane would take 64 registers)
+__device__ __forceinline__ f32x16 pixel_ws_load16(const float* ws_wave, int lane, int lt) {
+  const float* b = ws_wave + (size_t)lt * 1024;
+  asm volatile("" : "+s"(b));
+  const f32x4* p = reinterpret_cast<const f32x4*>(b) + lane;
+  const f32x4 a = p[0], c1 = p[64], c2 = p[128], d = p[192];
+  f32x16 v;
+  v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
+  v[4] = c1[0]; v[5] = c1[1]; v[6] = c1[2]; v[7] = c1[3];
+  v[8] = c2[0]; v[9] = c2[1]; v[10] = c2[2]; v[11] = c2[3];
+  v[12] = d[0]; v[13] = d[1]; v[14] = d[2]; v[15] = d[3];
+  return v;
+}
+
+// the initial accumulators of layers 0 and 2 of MLP `head` for one point: in the image, per output tile, the sum over the 16 taps
+// (row-major) of w_t P[tap] (fp32 FMA) and then + b - one lane's 16 rows of a tile are 4 aligned float4 per tap; outside, the
+// constants block's fold of the channel mean (hc, LDS).  Written to the workspace `ws` of this workgroup.
+__device__ __forceinline__ void pixel_prologue(const PixelParams& q, const float* hc, float* ws_wave, int lane, int head, int half,
+                                               float x0, float x1, float x2) {
+  const PixelTaps tp = pixel_taps(q, x0, x1, x2);
+  const size_t hw = (size_t)q.H * q.W;
+  const CstOffsets co = cst_offsets(2);
+#pragma unroll 1
+  for (int lt = 0; lt < 2 * kTilesHidden; ++lt) {
+    const int layer = lt / kTilesHidden, t = lt % kTilesHidden;
+    f32x16 g = load_bias16(hc + (layer ? co.c2 : co.c0) + (t * 2 + half) * 16);
+    if (tp.in) {
+      const float* base = q.proj + ((size_t)(head * 2 + layer) * hw) * kHidden + (t * 2 + half) * 16;
+      const f32x4* b4 = reinterpret_cast<const f32x4*>(q.cstb + (size_t)head * co.floats + (layer ? co.c2 : co.c0) + (t * 2 + half) * 16);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) g[r] = 0.0f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float w = __fmul_rn(tp.wy[i], tp.wx[j]);
+          const f32x4* src = reinterpret_cast<const f32x4*>(base + (size_t)(tp.row[i] + tp.col[j]) * kHidden);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const f32x4 pv = src[c];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) g[c * 4 + r] = fmaf(w, pv[r], g[c * 4 + r]);
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const f32x4 bv = b4[c];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) g[c * 4 + r] = __fadd_rn(bv[r], g[c * 4 + r]);
+      }
+    }
+    f32x4* dst = reinterpret_cast<f32x4*>(ws_wave + (size_t)lt * 1024) + lane;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dst[c * 64] = f32x4{g[c * 4], g[c * 4 + 1], g[c * 4 + 2], g[c * 4 + 3]};
+  }
+}
+
 // p.num_mlps = 2: SeparateDecoder (two MLPs, one output each); 1: CombinedDecoder (one MLP, two outputs).  The head loop
 // keeps a runtime trip count on purpose (with a compile-time single trip the compiler hoists ~1400 loop-invariant
 // values out of the tile loop and spills them); TWO_OUT selects, at compile time, whether the second last-layer row
@@ -83,8 +206,11 @@ __device__ __forceinline__ float nerf_feature(int f, float x0, float x1, float x
 // KP = K-steps taken by the point features in layers 0 and 2: 2 = (affine) xyz, 5 / 8 = NeRF encoding of 9 / 15 features.
 // CLS adds the part classifier of the label pass (classifier_head = Linear(512, num_class) on the last hidden activation
 // of MLP 0, networks/model.py:134-137,161-162 / :257-259,306-307): kMaxClasses more rows of the fused last layer.
-template <int ABL, int KP, bool TWO_OUT, bool CLS = false>
-__device__ __forceinline__ void sdf_mlp_body(const DecodeParams& p) {
+// PA (k1pa_kernels.hip; KP == 2, SeparateDecoder, no classifier): the latent of each point is pixel-aligned - layers 0 and 2 start
+// their accumulators from pixel_gather16 for in-image points (px: the sample's PixelParams); clear = the code above, unchanged.
+template <int ABL, int KP, bool TWO_OUT, bool CLS = false, bool PA = false>
+__device__ __forceinline__ void sdf_mlp_body(const DecodeParams& p, const PixelParams* px = nullptr) {
+  static_assert(!PA || (KP == 2 && !TWO_OUT && !CLS), "the pixel-aligned form is built for SeparateDecoder with xyz features");
   using CL = CstLayout<KP>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* ring = smem;
@@ -172,6 +298,7 @@ __device__ __forceinline__ void sdf_mlp_body(const DecodeParams& p) {
 #pragma unroll
         for (int s = 0; s < KP; ++s) bp[s] = 2 * s + half < p.pf ? nerf_feature(2 * s + half, x0, x1, x2) : 0.0f;
       }
+      if constexpr (PA) pixel_prologue(*px, hc, pixel_ws(*px, wave), lane, head, half, x0, x1, x2);
       // source of stage (s + 3) of this head's stream, wrapping to its start for the next tile; the base is made
       // opaque per tile so that the 128 x 4 per-lane source addresses are not hoisted out of the tile loop (spills)
       const float* sbase = sbase0;
@@ -185,6 +312,7 @@ __device__ __forceinline__ void sdf_mlp_body(const DecodeParams& p) {
 #pragma unroll
       for (int t = 0; t < kTilesHidden; ++t) {
         f32x16 acc = load_bias16(hc + CL::kC0 + (t * 2 + half) * 16);
+        if constexpr (PA) acc = pixel_ws_load16(pixel_ws(*px, wave), lane, t);
         if (!(ABL & 8)) {
 #pragma unroll
           for (int s = 0; s < KP; ++s) acc = ASDF_MFMA(hc[CL::kA0 + (t * KP + s) * 64 + lane], bp[s], acc);
@@ -222,6 +350,7 @@ __device__ __forceinline__ void sdf_mlp_body(const DecodeParams& p) {
       for (int t = 0; t < kTilesHidden; ++t) {
         f32x16& acc = acc2[t & 1];
         acc = load_bias16(hc + CL::kC2 + (t * 2 + half) * 16);
+        if constexpr (PA) acc = pixel_ws_load16(pixel_ws(*px, wave), lane, kTilesHidden + t);
 #pragma unroll
         for (int s = 0; s < KP; ++s) acc = ASDF_MFMA(hc[CL::kA2 + (t * KP + s) * 64 + lane], bp[s], acc);
         auto epi = [&]() {

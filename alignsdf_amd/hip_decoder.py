@@ -171,10 +171,27 @@ def unsupported_reason(state_dict, latent_size, point_feat_size, encode_style):
     return None
 
 
+def pixel_align_refusal(combined, point_feat_size, encode_style, num_class):
+    """Why (a string) the native pixel-aligned path (HipSdfDecoder(pixel_align=True): the pixel-aligned form of the fp32 chain,
+    csrc/k1pa_kernels.hip) does not cover a decoder of this shape, or None.  It is built for SeparateDecoder with EncodeStyle "nerf"
+    and PointFeatSize 3 - the point encoding of every shipped config - without the part classifier."""
+    if combined:
+        return "CombinedDecoder (the pixel-aligned kernel is built for SeparateDecoder)"
+    if num_class:
+        return "part classifier / label pass"
+    if encode_style != "nerf":
+        return "kinematic EncodeStyle %r" % (encode_style,)
+    if int(point_feat_size) > 3:
+        return "NeRF encoding with PointFeatSize %d (3 is built)" % int(point_feat_size)
+    return None
+
+
 class HipSdfDecoder:
     """Device-resident packed decoder.  One instance per (module, device)."""
 
-    def __init__(self, module_or_state_dict, latent_size=None, point_feat_size=None, encode_style=None, device=None):
+    def __init__(self, module_or_state_dict, latent_size=None, point_feat_size=None, encode_style=None, device=None, pixel_align=False):
+        """pixel_align=True: the decoder of a PixelAlign model (specs["PixelAlign"]) - samples are bound with set_sample_pixel and every
+        sweep runs the pixel-aligned form of the fp32 chain (csrc/k1pa_kernels.hip); see pixel_align_refusal for what it covers."""
         if isinstance(module_or_state_dict, torch.nn.Module):
             m = module_or_state_dict
             sd = m.state_dict()
@@ -241,7 +258,18 @@ class HipSdfDecoder:
                               "asdf_decoder_set_classifier")
             self.num_class = int(cw.shape[0])
         self._pf = pf
+        self.pixel_align = False
+        if pixel_align:
+            why = pixel_align_refusal(self.combined, self.point_feat_size, self.encode_style, self.num_class)
+            if why is not None:
+                raise NotImplementedError("the native pixel-aligned path does not cover this decoder: %s" % why)
         self._init_sweep_state()
+        if pixel_align:
+            # the fp32 chain only, ordinary sweeps only: ASDF_MATH / ASDF_FAST / ASDF_COARSE / ASDF_FINE are not applied (sweep_report)
+            self._fast_not_applied = {k: os.environ[k] for k in ("ASDF_MATH", "ASDF_FAST", "ASDF_COARSE", "ASDF_FINE") if os.environ.get(k)}
+            self.set_math("f32")
+            self.coarse_mode = self.fine_mode = "exact"
+            self.pixel_align = True
 
     def _init_sweep_state(self):
         """Everything the sweep state machine keeps on the host (arithmetic in use, calibration of the activation scales, modes,
@@ -329,12 +357,17 @@ class HipSdfDecoder:
 
     def set_fast(self, on=True):
         """Opt in to (or out of) the audited one-plane sweeps for mesh-producing calls: coarse "box" + fine "band" (what ASDF_FAST=1 /
-        `--fast` select when the decoder is packed), or ordinary sweeps in both passes - the default."""
+        `--fast` select when the decoder is packed), or ordinary sweeps in both passes - the default.  A pixel-aligned decoder has
+        ordinary sweeps only: set_fast(True) raises."""
+        if on and getattr(self, "pixel_align", False):
+            raise ValueError("a pixel-aligned decoder runs ordinary fp32 sweeps only: the one-plane sweeps (--fast) do not cover it")
         self.coarse_mode, self.fine_mode = (FAST_COARSE, FAST_FINE) if on else ("exact", "exact")
 
     def set_math(self, math):
         """Select the arithmetic of the hidden GEMMs ("f32" / "f16x3"); raises for NeRF-encoded decoders and f16x3."""
         code = {"f32": _native.MATH_F32, "f16x3": _native.MATH_F16X3}[math]
+        if math != "f32" and getattr(self, "pixel_align", False):
+            raise ValueError("a pixel-aligned decoder runs the fp32 MFMA chain only (math='f32'), not %r" % math)
         _native.check(self._L.asdf_decoder_set_math(self._h, code), "asdf_decoder_set_math")
         self.math = math
 
@@ -510,6 +543,8 @@ class HipSdfDecoder:
         1 KB is a shader blit that cannot get a wave slot while a persistent sweep owns every compute unit (round 5's eval-mode
         trace: 21.5 ms per sample resident), and a plain `.to(device)` of pageable memory makes the caller wait
         for everything queued."""
+        if getattr(self, "pixel_align", False):
+            raise ValueError("a pixel-aligned decoder binds its samples with set_sample_pixel (feature map, cam_intr, root joint)")
         if latent_vec.numel() != self.latent_size:
             raise ValueError("latent has %d elements, expected %d" % (latent_vec.numel(), self.latent_size))
         host = latent_vec.device.type == "cpu"
@@ -548,6 +583,30 @@ class HipSdfDecoder:
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(self.device))
                 slot[2] = ev
+
+    def set_sample_pixel(self, feat, cam_intr, root_joint, image_size, scale_factor):
+        """Bind one PixelAlign sample (utils/utils.py:536-566): the HeadNet feature map `feat` [1, LatentSize, H, W] (H, W <= 256),
+        `cam_intr` [1, 3, 4] (or [3, 4]), the root joint `root_joint` (mano_results["joints"][:, 0], camera space, 3 values),
+        specs["ImageSize"][0] and specs["SdfScaleFactor"] (asdf_decoder_set_sample_pixel).  The map stays referenced until the next
+        bind: the projection kernels read it in stream order."""
+        if not getattr(self, "pixel_align", False):
+            raise ValueError("set_sample_pixel needs a decoder built with pixel_align=True")
+        f = torch.as_tensor(feat).detach()
+        if f.dim() != 4 or f.shape[0] != 1:
+            raise ValueError("feature map of shape %s: [1, C, H, W] expected (batch 1)" % (tuple(f.shape),))
+        cam = np.asarray(torch.as_tensor(cam_intr).detach().cpu(), dtype=np.float32).reshape(-1)
+        root = np.asarray(torch.as_tensor(root_joint).detach().cpu(), dtype=np.float32).reshape(-1)
+        if cam.size != 12 or root.size != 3:
+            raise ValueError("cam_intr needs 3 x 4 values and root_joint 3 (batch 1), got %d and %d" % (cam.size, root.size))
+        f = f.to(device=self.device, dtype=torch.float32).contiguous()
+        _, C, H, W = (int(v) for v in f.shape)
+        self._bound = (f, None)
+        self._latent = f
+        with torch.cuda.device(self.device):
+            _native.check(self._L.asdf_decoder_set_sample_pixel(self._h, f.data_ptr(), C, H, W, (ctypes.c_float * 12)(*cam.tolist()),
+                                                                 (ctypes.c_float * 3)(*root.tolist()), ctypes.c_float(float(image_size)),
+                                                                 ctypes.c_float(float(scale_factor)), self._stream()),
+                          "asdf_decoder_set_sample_pixel")
 
     def decode_grid(self, N, origin3, voxel_size, grid_mode=_native.GRID_REFERENCE, want_bbox=True, hand=True, obj=True,
                     check_range=None, lattice=None):
@@ -1200,7 +1259,11 @@ class HipSdfDecoder:
                       "cert": {k: 0 for k in self._ADDITIVE_CERT}, "math": self.math, "modes": (self.coarse_mode, self.fine_mode)}
         d = lambda now, then, k: int(now[k]) - int(then[k])
         c = self.cert
-        return {
+        extra = {}
+        if getattr(self, "pixel_align", False):
+            extra["pixel_align"] = {"path": "native (fp32 MFMA chain, pixel-aligned form)", "fast_sweeps": "not applied: a pixel-aligned "
+                                    "decoder runs ordinary fp32 sweeps only", "ignored_settings": dict(self._fast_not_applied)}
+        return dict(extra, **{
             "evaluator": "hip kernels (libalignsdf_hip.so)",
             "arithmetic": {"at_start": z["math"], "now": self.math,
                            "fell_back_to_fp32_chain": z["math"] == "f16x3" and self.math == "f32"},
@@ -1226,7 +1289,7 @@ class HipSdfDecoder:
             "lattice_max_error": {"coarse_lattice": c["lattice_max_error"], "zoom_lattice": c["fine_lattice_max_error"]},
             "allowance_now": self._box_tau, "audit_voxels_per_sweep_and_head": self.audit_voxels,
             "rule": {"tau_factor": TAU_FACTOR, "tau_accept": TAU_ACCEPT, "recalibrate_every": RECAL_EVERY, "tail_max": TAIL_MAX},
-        }
+        })
 
     def decode_points(self, xyz):
         """Both heads on explicit normalised points [M,3]. Returns (hand [M], obj [M]) device tensors."""

@@ -5,11 +5,13 @@ through the HIP path (or, for the variants the kernels do not cover, through the
 normalised xyz [M,3] (PointFeatSize 3, or with `raw_xyz=True` plus pose dicts so the affine embedding is
 folded into the kernel) - embedded [M,pf] queries of a pose-aligned model cannot be un-embedded and raise.
 """
+import logging
+import os
 import weakref
 
 import torch
 
-from ..hip_decoder import HipSdfDecoder, kinematic_affine
+from ..hip_decoder import HipSdfDecoder, kinematic_affine, pixel_align_refusal
 
 _cache = weakref.WeakKeyDictionary()
 
@@ -19,33 +21,78 @@ def _param_fingerprint(module):
     return tuple((p.data_ptr(), p._version) for p in module.parameters())
 
 
-def hip_decoder_for(decoder, device=None):
+def hip_decoder_for(decoder, device=None, pixel_align=False):
     """Packed HIP decoder of an nn.Module, built once per (module, device) and cached; re-packed when the module's
-    parameters have changed since (the reference reconstructs from inside the training loop, train.py:668)."""
+    parameters have changed since (the reference reconstructs from inside the training loop, train.py:668).  pixel_align=True: the
+    decoder's pixel-aligned form (HipSdfDecoder(pixel_align=True)), cached on its own."""
     if isinstance(decoder, HipSdfDecoder):
         return decoder
     dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
     per_mod = _cache.setdefault(decoder, {})
     fp = _param_fingerprint(decoder)
-    hit = per_mod.get(str(dev))
+    key = str(dev) + (":pixel_align" if pixel_align else "")
+    hit = per_mod.get(key)
     if hit is None or hit[0] != fp:
         if hit is not None:
             hit[1].close()
-        per_mod[str(dev)] = (fp, HipSdfDecoder(decoder, device=dev))
-    return per_mod[str(dev)][1]
+        per_mod[key] = (fp, HipSdfDecoder(decoder, device=dev, pixel_align=pixel_align))
+    return per_mod[key][1]
 
 
-def decoder_for(decoder, specs=None, mano_results=None, device=None):
+PIXEL_ALIGN_MODES = ("module", "native")
+
+
+def pixel_align_mode(pixel_align=None):
+    """How a PixelAlign decoder is evaluated: `pixel_align` if given, else ASDF_PIXEL_ALIGN, else "module" (the module on
+    PyTorch-ROCm); "native" = the pixel-aligned HIP kernel where it covers the decoder."""
+    mode = pixel_align if pixel_align is not None else (os.environ.get("ASDF_PIXEL_ALIGN", "") or "module")
+    if mode not in PIXEL_ALIGN_MODES:
+        raise ValueError("pixel_align / ASDF_PIXEL_ALIGN must be 'module' or 'native', not %r" % (mode,))
+    return mode
+
+
+def native_pixel_align_refusal(decoder, specs, mano_results):
+    """Why (a string) the native pixel-aligned path cannot take this PixelAlign decoder / sample, or None."""
+    from ..torch_decoder import needs_module_path
+    if not isinstance(decoder, torch.nn.Module):
+        return "not an nn.Module"
+    why = needs_module_path(decoder, dict(specs, PixelAlign=False), mano_results)
+    if why is not None:
+        return why
+    combined = "lin0.bias" in dict(decoder.named_parameters())
+    classifier = bool(getattr(decoder, "use_classifier", False) or specs.get("ClassifierBranch", False))
+    why = pixel_align_refusal(combined, specs["PointFeatSize"], specs["EncodeStyle"], int(classifier))
+    if why is not None:
+        return why
+    if mano_results is None or "joints" not in mano_results:
+        return "no mano_results['joints']: the root joint places the points in the camera frame"
+    return None
+
+
+def decoder_for(decoder, specs=None, mano_results=None, device=None, pixel_align=None):
     """The evaluator of this decoder for this kind of sample: the packed HIP decoder wherever the kernels cover the variant,
     otherwise the module itself on PyTorch-ROCm (alignsdf_amd.torch_decoder: use_tanh / LayerNorm / xyz_in_all / PixelAlign /
-    pose-aligned model without mano_results) - the stock-module path of SURVEY 8 b2."""
+    pose-aligned model without mano_results) - the stock-module path of SURVEY 8 b2.
+
+    A PixelAlign decoder stays on the module path unless `pixel_align="native"` (or ASDF_PIXEL_ALIGN=native) opts in to the
+    pixel-aligned HIP kernel; a decoder or sample that kernel does not cover (native_pixel_align_refusal) then keeps the module path."""
     from ..torch_decoder import TorchModuleDecoder, needs_module_path
+    mode = pixel_align_mode(pixel_align)
     if isinstance(decoder, (HipSdfDecoder, TorchModuleDecoder)):
         if isinstance(decoder, HipSdfDecoder):
+            if getattr(decoder, "pixel_align", False):
+                if specs is not None and not specs.get("PixelAlign", False):
+                    raise ValueError("a pixel-aligned decoder evaluates PixelAlign samples only")
+                return decoder
             why = needs_module_path(None, specs, mano_results)
             if why:
                 raise NotImplementedError("%s - pass the nn.Module so that it can be called" % why)
         return decoder
+    if specs is not None and specs.get("PixelAlign", False) and mode == "native":
+        refused = native_pixel_align_refusal(decoder, specs, mano_results)
+        if refused is None:
+            return hip_decoder_for(decoder, device, pixel_align=True)
+        logging.warning("native pixel-aligned path refused (%s): the decoder stays on the module path", refused)
     why = needs_module_path(decoder, specs, mano_results)
     if why is None:
         return hip_decoder_for(decoder, device)
@@ -60,7 +107,11 @@ def decoder_for(decoder, specs=None, mano_results=None, device=None):
 
 def bind_sample(dec, specs, latent_vec, mano_results, obj_results, cam_intr=None):
     """Bind one sample's codes to an evaluator returned by decoder_for."""
-    if isinstance(dec, HipSdfDecoder):
+    if isinstance(dec, HipSdfDecoder) and getattr(dec, "pixel_align", False):
+        if cam_intr is None or mano_results is None:
+            raise ValueError("a PixelAlign sample needs cam_intr and mano_results['joints']")
+        dec.set_sample_pixel(latent_vec, cam_intr, mano_results["joints"][:, 0], specs["ImageSize"][0], specs["SdfScaleFactor"])
+    elif isinstance(dec, HipSdfDecoder):
         dec.set_sample(latent_vec, sample_embedding(specs, mano_results, obj_results, dec.combined))
     else:
         dec.set_sample(latent_vec, mano_results, obj_results, cam_intr)

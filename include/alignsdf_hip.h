@@ -94,6 +94,18 @@ int asdf_decoder_set_sample(asdf_decoder_t* dec, const float* latent_dev, const 
  * takes part (such a blit cannot get a wave slot while a persistent sweep owns every compute unit: 21.5 ms per sample resident in
  * the round-5 eval-mode trace). */
 int asdf_decoder_set_sample_host(asdf_decoder_t* dec, const float* latent_pinned, const float* embed_pinned, void* stream);
+/* Bind a PIXEL-ALIGNED sample (specs["PixelAlign"], utils/utils.py:536-566) instead of a latent code: the latent of a query point
+ * is the bicubic grid_sample (align_corners, zero padding) of the feature map feat_dev [C][H][W] (device, batch 1) at the point's
+ * projection  uv = (cam3x4 . (xyz * 2 / scale_factor + root3, 1)).xy / z / image_size * 2 - 1, or - for a point outside
+ * -1 <= u, v <= 1 (NaN / inf included) - the map's channel mean.  grid_sample is linear in the map, so the latent columns of layers 0
+ * and 2 are projected once per sample (P = W_lat . F per pixel, decoder-owned memory that grows on demand: 32 MiB at 64 x 64) and
+ * the kernel gathers 16 taps of P per point; the mean takes the ordinary fold.  cam3x4 (row-major cam_intr) and root3 (the root
+ * joint, camera space) are host arrays.  SeparateDecoder with xyz point features (PointFeatSize 3) only; C must equal LatentSize
+ * and H, W lie in [1, 256] - anything else is ASDF_EINVAL.  Until the next asdf_decoder_set_sample*, lattice sweeps
+ * (asdf_decode_grid / _dev) and asdf_decode_points run on the fp32 MFMA chain (ASDF_MATH_F32 - other arithmetic, the one-plane
+ * sweeps and the label pass return ASDF_EINVAL). */
+int asdf_decoder_set_sample_pixel(asdf_decoder_t* dec, const float* feat_dev, int32_t C, int32_t H, int32_t W, const float cam3x4[12],
+                                  const float root3[3], float image_size, float scale_factor, void* stream);
 
 /* Evaluate both heads on the N^3 lattice
  *     coord[a] = idx[a] * voxel_size + origin[a]     (fp32 mul then add, a = 0,1,2; axis 2 fastest)
