@@ -36,6 +36,24 @@ EXPORTS = (
 MATH_F32, MATH_F16X3 = 0, 1
 MAX_CLASSES = 8
 
+# The integer records of the sweeps and the capacities of their voxel lists: include/alignsdf_hip.h's ASDF_BOX_* / ASDF_STATUS_* /
+# ASDF_REC_* / ASDF_*_CAP under the same names without the prefix (tests/test_record_layout.py holds the two together)
+BOX_MIN, BOX_MAX, BOX_COUNT, BOX_RANGE, BOX_STRIDE, BOX_WORDS = 0, 3, 6, 7, 8, 16
+BOX_CLUSTER_FAULT_BIT, BOX_NEAR_OVERFLOW_BIT, BOX_RANGE_MASK = 0x20000000, 0x40000000, 0x1fffffff
+STATUS_RANGE, STATUS_LIST_OVERFLOW, STATUS_FIXUP, STATUS_MAX_ERR = 0, 1, 2, 3
+STATUS_PEAK, STATUS_PEAK_STRIDE, STATUS_CLUSTER_FAULT, STATUS_CLOCK, STATUS_WORDS = 4, 4, 11, 12, 16
+REC_STATUS, REC_CANDIDATES, REC_BAND = 16, 32, 33
+REC_AUDIT_MAX_ERR, REC_AUDIT_FLIPS, REC_AUDIT_EVALS, REC_NEAR_OVERFLOW = 35, 36, 37, 38
+REC_SHELL_PICKS, REC_SHELL_POPULATION, REC_AUDIT_SUMSQ, REC_WORDS = 39, 40, 41, 48
+NEAR_CAP, CAND_CAP, BAND_CAP = 1 << 16, 1 << 21, 1 << 22
+BOX_RANGE_WORDS = (BOX_RANGE, BOX_STRIDE + BOX_RANGE)      # the range words of the hand / object head in a box record
+
+
+def box_of(rec, head):
+    """(min[3], max[3], count) of one head's box in a box / sweep record."""
+    o = BOX_STRIDE * head
+    return rec[o + BOX_MIN:o + BOX_MIN + 3], rec[o + BOX_MAX:o + BOX_MAX + 3], int(rec[o + BOX_COUNT])
+
 
 class NativeError(RuntimeError):
     def __init__(self, code, what):

@@ -15,3 +15,10 @@ extern thread_local int g_last_hip_error;
       return asdf_e_ == hipErrorOutOfMemory ? ASDF_ENOMEM : ASDF_EHIP; \
     }                                                          \
   } while (0)
+
+// Evaluate a call that returns an ASDF_* code; anything but ASDF_OK is returned from the enclosing function.
+#define ASDF_TRY(expr)                                         \
+  do {                                                         \
+    const int asdf_rc_ = (expr);                               \
+    if (asdf_rc_ != ASDF_OK) return asdf_rc_;                  \
+  } while (0)

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sdf_layout.h"
+#include "sweep_records.h"
 
 namespace asdf {
 
@@ -55,7 +56,7 @@ struct DecodeParams {
   float* sdf0;              // [P] hand SDF (may be null)
   float* sdf1;              // [P] object SDF (may be null)
   const float* xyz;         // [P][3] when mode == kPointList
-  int* bbox;                // [kHeads][8]: min0,min1,min2,max0,max1,max2,count,pad (or null)
+  int* bbox;                // the box record (ASDF_BOX_*, include/alignsdf_hip.h), or null
   const int* idx;           // kGridSubset: [<= P] linear lattice indices
   const int* count_dev;     // kGridSubset: number of listed points (device word; P is the capacity)
   int short_max;            // kGridSubset, fp32 chain: lists of up to this many points belong to the short-list form
@@ -66,12 +67,12 @@ struct DecodeParams {
   int grid_mode;            // kGridSubset: kGridReference / kGridInteger of the lattice
   int* fixup_flag;          // kGridSubset with bbox: the outputs REPLACE earlier values - the box is patched in place (a voxel
                             // that turns negative extends it) and *fixup_flag is raised when one turns non-negative
-  int* status;              // decoder-owned status record: [0] += lanes whose activations left the fp16 range (K1h only)
+  int* status;              // decoder-owned status record (ASDF_STATUS_*)
   int* audit;               // split-half kGridSubset only: the audit record of a one-plane sweep (or null).  List positions
                             // >= *audit_from (all of them when audit_from is null) are AUDIT picks - voxels the one-plane sweep
-                            // decided by sign alone, drawn at random and re-evaluated to check that decision: [0] = largest
-                            // |new - old| over them (float bits), [1] += picks whose sign changed, [2] += picks evaluated;
-                            // the other positions report to status[3] as usual
+                            // decided by sign alone, drawn at random and re-evaluated to check that decision (sweep_records.h:
+                            // kAuditMaxErr / kAuditFlips / kAuditEvals / kAuditSumSq); the other positions report to
+                            // ASDF_STATUS_MAX_ERR as usual
   const int* audit_from;
   const float* a16;         // one-plane kernels (affine point features): [heads][kA16Floats] - the point-feature columns and bias rows
                             // of layers 0 and 2 as fp16 A operands of ONE v_mfma_f32_32x32x16_f16 per tile (fold_points_f16_kernel)

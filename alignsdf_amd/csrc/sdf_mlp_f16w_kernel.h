@@ -203,7 +203,7 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
   const unsigned lds_ring_base = (unsigned)(size_t)(__attribute__((address_space(3))) float*)ring;
   // shader-clock stamps of workgroup 0 around a whole-lattice sweep (status words 12..13 begin, 14..15 end): bench.py's clock and
   // matrix-pipe utilisation
-  if (!SUB && p.status && p.mode != kPointList && blockIdx.x == 0 && tid == 0) reinterpret_cast<long long*>(p.status + 12)[0] = clock64();
+  if (!SUB && p.status && p.mode != kPointList && blockIdx.x == 0 && tid == 0) reinterpret_cast<long long*>(p.status + ASDF_STATUS_CLOCK)[0] = clock64();
 
 #pragma unroll 1
   for (int slot = 0; slot < p.num_mlps; ++slot) {
@@ -212,6 +212,7 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
     // negative-voxel bounding box of this MLP's output + the range report, one record per wave in LDS: [0..2] min index, [3..5] max
     // index, [6] count, [7] lanes whose activations left the fp16 range (or whose output is not in [-1, 1]); [16..18] activation peaks
     int* wrec = reinterpret_cast<int*>(cst + CL::kFloats) + wave * kWrecInts;
+    // (empty_box_word written out: the call changes this kernel's ISA)
     if (lane < kWrecInts) wrec[lane] = lane >= 16 ? 0 : ((lane & 7) < 3 ? 0x7fffffff : ((lane & 7) < 6 ? -1 : 0));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -484,7 +485,7 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
       const bool is_hand = head == 0;
       if (SUB) {
         // subset mode replaces values: the largest change is the measured error of the arithmetic it corrects.  Marked voxels report
-        // to status[3]; audit picks (voxels the one-plane sweep decided by sign alone) to the audit record, together with the number
+        // to ASDF_STATUS_MAX_ERR; audit picks (voxels the one-plane sweep decided by sign alone) to the audit record, together with the number
         // of picks whose sign the exact value contradicts.  Reduced over the wave on the float BITS (a NaN is a huge pattern and must
         // survive the reduction), then one set of atomics per wave.
         int dm = 0, da = 0, flips = 0, na = 0;
@@ -509,10 +510,10 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
           if (p.audit) sq += __shfl_xor(sq, m);
         }
         if (lane == 0) {
-          if (p.status && dm) atomicMax(p.status + 3, dm);
+          if (p.status && dm) atomicMax(p.status + ASDF_STATUS_MAX_ERR, dm);
           if (p.audit && na) {
-            atomicMax(p.audit + 0, da); if (flips) atomicAdd(p.audit + 1, flips); atomicAdd(p.audit + 2, na);
-            atomicAdd(reinterpret_cast<float*>(p.audit + 3), sq);
+            atomicMax(p.audit + kAuditMaxErr, da); if (flips) atomicAdd(p.audit + kAuditFlips, flips); atomicAdd(p.audit + kAuditEvals, na);
+            atomicAdd(reinterpret_cast<float*>(p.audit + kAuditSumSq), sq);
           }
         }
       } else if (valid && half == 0) {
@@ -564,23 +565,23 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
       // one set of atomics per wave: record 0 = hand (MLP 0), record 1 = object (MLP 1); word 7: lanes out of range (0 unless the
       // fp16 planes overflowed; the host then re-calibrates)
       if (p.bbox && p.mode != kPointList) {
-        int* out = p.bbox + (head == 0 ? 0 : 8);
-        if (wrec[6]) {
-          atomicMin(out + 0, wrec[0]); atomicMin(out + 1, wrec[1]); atomicMin(out + 2, wrec[2]);
-          atomicMax(out + 3, wrec[3]); atomicMax(out + 4, wrec[4]); atomicMax(out + 5, wrec[5]);
-          atomicAdd(out + 6, wrec[6]);
+        int* out = p.bbox + (head == 0 ? 0 : ASDF_BOX_STRIDE);
+        if (wrec[6]) {      // (not flush_box: reading the LDS record up front instead of word by word changes this kernel's ISA)
+          atomicMin(out + ASDF_BOX_MIN + 0, wrec[0]); atomicMin(out + ASDF_BOX_MIN + 1, wrec[1]); atomicMin(out + ASDF_BOX_MIN + 2, wrec[2]);
+          atomicMax(out + ASDF_BOX_MAX + 0, wrec[3]); atomicMax(out + ASDF_BOX_MAX + 1, wrec[4]); atomicMax(out + ASDF_BOX_MAX + 2, wrec[5]);
+          atomicAdd(out + ASDF_BOX_COUNT, wrec[6]);
         }
-        if (wrec[7]) atomicAdd(p.bbox + (head == 0 ? 7 : 15), wrec[7]);
+        if (wrec[7]) atomicAdd(p.bbox + (head == 0 ? ASDF_BOX_RANGE : ASDF_BOX_STRIDE + ASDF_BOX_RANGE), wrec[7]);
       }
       if (p.status) {
-        if (wrec[7]) atomicAdd(p.status, wrec[7]);
-        int* peak = p.status + 4 + 4 * head;       // [4..6] MLP 0, [8..10] MLP 1: largest plane value of h0 / h1 / h2 (float bits)
+        if (wrec[7]) atomicAdd(p.status + ASDF_STATUS_RANGE, wrec[7]);
+        int* peak = p.status + ASDF_STATUS_PEAK + ASDF_STATUS_PEAK_STRIDE * head;       // largest plane value of h0 / h1 / h2 (float bits)
         atomicMax(peak + 0, wrec[16]); atomicMax(peak + 1, wrec[17]); atomicMax(peak + 2, wrec[18]);
       }
     }
   }   // MLPs
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (!SUB && p.status && p.mode != kPointList && blockIdx.x == 0 && tid == 0) reinterpret_cast<long long*>(p.status + 12)[1] = clock64();
+  if (!SUB && p.status && p.mode != kPointList && blockIdx.x == 0 && tid == 0) reinterpret_cast<long long*>(p.status + ASDF_STATUS_CLOCK)[1] = clock64();
 }
 
 // The __global__ instantiations live in k1hw_kernels.hip; tools/k1h_ablate.hip (-DWIDE=1) instantiates its own.

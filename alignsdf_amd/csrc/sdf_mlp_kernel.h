@@ -440,8 +440,8 @@ __device__ __forceinline__ void sdf_mlp_body(const DecodeParams& p, const PixelP
         float* out = is_hand ? p.sdf0 : p.sdf1;
         if (p.mode == kGridSubset && p.status && !p.bbox) {
           // re-evaluation without a box to patch (the narrow-band fine sweep): only the measured error of what it replaces
-          if (out) atomicMax(p.status + 3, __float_as_int(fabsf(sdf - out[po])));
-          if (combined && p.sdf1) atomicMax(p.status + 3, __float_as_int(fabsf(sdfb - p.sdf1[po])));
+          if (out) atomicMax(p.status + ASDF_STATUS_MAX_ERR, __float_as_int(fabsf(sdf - out[po])));
+          if (combined && p.sdf1) atomicMax(p.status + ASDF_STATUS_MAX_ERR, __float_as_int(fabsf(sdfb - p.sdf1[po])));
         }
         if (p.mode == kGridSubset && p.bbox) {
           // refinement of an existing volume: patch the negative-voxel box for every sign change instead of recounting
@@ -449,20 +449,18 @@ __device__ __forceinline__ void sdf_mlp_body(const DecodeParams& p, const PixelP
             const float before = vol[po];
             const bool was = before < p.neg_thr, is = now < 0.0f;
             // the largest change this pass made to a value (float bits): the measured error of the arithmetic it corrects
-            if (p.status) atomicMax(p.status + 3, __float_as_int(fabsf(now - before)));
+            if (p.status) atomicMax(p.status + ASDF_STATUS_MAX_ERR, __float_as_int(fabsf(now - before)));
             if (was == is) return;
             if (is) {
               int i0, i1, i2;
               lattice_ijk(po, p.N, i0, i1, i2);
-              atomicMin(rec + 0, i0); atomicMin(rec + 1, i1); atomicMin(rec + 2, i2);
-              atomicMax(rec + 3, i0); atomicMax(rec + 4, i1); atomicMax(rec + 5, i2);
-              atomicAdd(rec + 6, 1);
+              flush_box(rec, i0, i1, i2, i0, i1, i2, 1);
             } else {
               atomicExch(p.fixup_flag, 1);        // the box may have to shrink: the caller recounts
             }
           };
-          if (out) patch(out, sdf, p.bbox + (is_hand ? 0 : 8));
-          if (combined && p.sdf1) patch(p.sdf1, sdfb, p.bbox + 8);
+          if (out) patch(out, sdf, p.bbox + (is_hand ? 0 : ASDF_BOX_STRIDE));
+          if (combined && p.sdf1) patch(p.sdf1, sdfb, p.bbox + ASDF_BOX_STRIDE);
         }
         if (out) out[po] = sdf;
         if (combined && p.sdf1) p.sdf1[po] = sdfb;
@@ -509,14 +507,10 @@ __device__ __forceinline__ void sdf_mlp_body(const DecodeParams& p, const PixelP
           b0_ = max(b0_, __shfl_xor(b0_, m)); b1_ = max(b1_, __shfl_xor(b1_, m)); b2_ = max(b2_, __shfl_xor(b2_, m));
           n += __shfl_xor(n, m);
         }
-        if (lane == 0 && n) {
-          atomicMin(rec + 0, a0_); atomicMin(rec + 1, a1_); atomicMin(rec + 2, a2_);
-          atomicMax(rec + 3, b0_); atomicMax(rec + 4, b1_); atomicMax(rec + 5, b2_);
-          atomicAdd(rec + 6, n);
-        }
+        if (lane == 0 && n) flush_box(rec, a0_, a1_, a2_, b0_, b1_, b2_, n);
       };
-      flush(p.bbox + (head == 0 ? 0 : 8), bmin0, bmin1, bmin2, bmax0, bmax1, bmax2, bcnt);
-      if (TWO_OUT) flush(p.bbox + 8, omin0, omin1, omin2, omax0, omax1, omax2, ocnt);
+      flush(p.bbox + (head == 0 ? 0 : ASDF_BOX_STRIDE), bmin0, bmin1, bmin2, bmax0, bmax1, bmax2, bcnt);
+      if (TWO_OUT) flush(p.bbox + ASDF_BOX_STRIDE, omin0, omin1, omin2, omax0, omax1, omax2, ocnt);
     }
   }   // MLPs
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -134,27 +134,25 @@ __device__ __forceinline__ void short_last_layer(const DecodeParams& p, const fl
     // what the tile form does with a kGridSubset result (sdf_mlp_kernel.h): measured change, box patch, value in place
     float* out = is_hand ? p.sdf0 : p.sdf1;
     if (p.status && !p.bbox) {
-      if (out) atomicMax(p.status + 3, __float_as_int(fabsf(sdf - out[po])));
-      if (TWO_OUT && p.sdf1) atomicMax(p.status + 3, __float_as_int(fabsf(sdfb - p.sdf1[po])));
+      if (out) atomicMax(p.status + ASDF_STATUS_MAX_ERR, __float_as_int(fabsf(sdf - out[po])));
+      if (TWO_OUT && p.sdf1) atomicMax(p.status + ASDF_STATUS_MAX_ERR, __float_as_int(fabsf(sdfb - p.sdf1[po])));
     }
     if (p.bbox) {
       auto patch = [&](float* vol, float now, int* rec) {
         const float before = vol[po];
         const bool was = before < p.neg_thr, is = now < 0.0f;
-        if (p.status) atomicMax(p.status + 3, __float_as_int(fabsf(now - before)));
+        if (p.status) atomicMax(p.status + ASDF_STATUS_MAX_ERR, __float_as_int(fabsf(now - before)));
         if (was == is) return;
         if (is) {
           int i0, i1, i2;
               lattice_ijk(po, p.N, i0, i1, i2);
-          atomicMin(rec + 0, i0); atomicMin(rec + 1, i1); atomicMin(rec + 2, i2);
-          atomicMax(rec + 3, i0); atomicMax(rec + 4, i1); atomicMax(rec + 5, i2);
-          atomicAdd(rec + 6, 1);
+          flush_box(rec, i0, i1, i2, i0, i1, i2, 1);
         } else {
           atomicExch(p.fixup_flag, 1);
         }
       };
-      if (out) patch(out, sdf, p.bbox + (is_hand ? 0 : 8));
-      if (TWO_OUT && p.sdf1) patch(p.sdf1, sdfb, p.bbox + 8);
+      if (out) patch(out, sdf, p.bbox + (is_hand ? 0 : ASDF_BOX_STRIDE));
+      if (TWO_OUT && p.sdf1) patch(p.sdf1, sdfb, p.bbox + ASDF_BOX_STRIDE);
     }
     if (out) out[po] = sdf;
     if (TWO_OUT && p.sdf1) p.sdf1[po] = sdfb;

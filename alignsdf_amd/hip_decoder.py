@@ -34,14 +34,11 @@ def fast_requested():
     return os.environ.get("ASDF_FAST", "0") not in ("", "0")
 
 
-BAND_CAP = 1 << 22           # voxels per head the narrow-band sweep can re-evaluate (csrc/decoder.hip: kBandCap)
-NEAR_CAP = 1 << 16           # near-level refinement list of a split-half sweep
-CAND_CAP = 1 << 21           # box candidates of one coarse sweep
+# the records of the sweeps and the capacities of their lists: one layout, include/alignsdf_hip.h, mirrored in _native
+from ._native import BAND_CAP, CAND_CAP, NEAR_CAP, REC_WORDS  # noqa: E402,F401
+from ._native import BOX_CLUSTER_FAULT_BIT as CLUSTER_FAULT_BIT, BOX_NEAR_OVERFLOW_BIT as NEAR_OVERFLOW_BIT  # noqa: E402
 AUDIT_VOXELS = 1 << 16        # per one-plane sweep and head (asdf_decoder_set_audit)
-NEAR_OVERFLOW_BIT = 0x40000000
-CLUSTER_FAULT_BIT = 0x20000000   # bit 29 of word 7 of a sweep's bbox record: the short-list kernel's cluster form reported a member that never arrived
 CODE_SLOTS = 16               # pinned staging slots for the per-sample codes of set_sample's host path
-REC_WORDS = 48                # record of a one-plane sweep (include/alignsdf_hip.h: asdf_decode_grid_box)
 # allowance tau = TAU_FACTOR x the estimated lattice maximum of |one-plane - exact| of recent sweeps; a sweep is accepted while ITS
 # estimate (and the error on its re-evaluated voxels) stays within TAU_ACCEPT x the tau it was launched with - a factor
 # TAU_FACTOR x TAU_ACCEPT = 3 of sample-to-sample head room (pose-aligned decoders vary by 2 x), 1 / TAU_ACCEPT = 1.67 of safety
@@ -379,16 +376,17 @@ class HipSdfDecoder:
 
     @staticmethod
     def _range_words(rec):
-        """(fp16 range violations, near-level list overflowed) of a bbox / sweep record: words 7 / 15, bit 30 = the flag."""
-        w = (int(rec[7]), int(rec[15]))
-        return sum(v & (CLUSTER_FAULT_BIT - 1) for v in w), bool((w[0] | w[1]) & NEAR_OVERFLOW_BIT)
+        """(fp16 range violations, near-level list overflowed) of a bbox / sweep record: the range words and their flag bit."""
+        w = [int(rec[k]) for k in _native.BOX_RANGE_WORDS]
+        return sum(v & _native.BOX_RANGE_MASK for v in w), bool((w[0] | w[1]) & NEAR_OVERFLOW_BIT)
 
     def _note_cluster_fault(self, rec):
         """Bit 29 of word 7 of a bbox record / word 16 + 11 of a one-plane sweep's record: a member of the short-list kernel's cluster
         form waited longer than its bound for another one (csrc/sdf_mlp_short_kernel.h).  The sweep the record belongs to is COMPLETE -
         the tile form behind the launch evaluated the list, same bits - and the form is switched off for this decoder, once, here
         (a recoverable failure instead of a trap that takes the HIP context along)."""
-        hit = bool(int(rec[7]) & CLUSTER_FAULT_BIT) or (len(rec) > 27 and int(rec[27]) != 0)
+        fault = _native.REC_STATUS + _native.STATUS_CLUSTER_FAULT
+        hit = bool(int(rec[_native.BOX_RANGE]) & CLUSTER_FAULT_BIT) or (len(rec) > fault and int(rec[fault]) != 0)
         if hit and not self._cluster_off:
             import logging
             logging.warning("short-list kernel: a member of a cluster did not arrive in time; the tile form evaluated the list, the cluster "
@@ -474,7 +472,7 @@ class HipSdfDecoder:
         new = cur.copy()
         for h in range(1 if self.combined else 2):
             for l in range(3):
-                bits = int(st[4 + 4 * h + l])
+                bits = int(st[_native.STATUS_PEAK + _native.STATUS_PEAK_STRIDE * h + l])
                 if bits == 0:
                     continue                                  # this MLP did not run (or produced only zeros)
                 self._cal_done[h, l] = True
@@ -675,15 +673,15 @@ class HipSdfDecoder:
         if guard:
             for _ in range(5):
                 st = self._status(clear=True)
-                if int(st[1]) and self.math == "f16x3":
+                if int(st[_native.STATUS_LIST_OVERFLOW]) and self.math == "f16x3":
                     # more near-level voxels than the refinement list holds: this sweep on the fp32 chain
                     self.set_math("f32")
                     ev = launch()
                     self.set_math("f16x3")
                     break
-                if not int(st[0]):
+                if not int(st[_native.STATUS_RANGE]):
                     break
-                self._recover(int(st[0]), st)
+                self._recover(int(st[_native.STATUS_RANGE]), st)
                 ev = launch()
         if once_f32:
             self.set_math("f16x3")
@@ -757,9 +755,10 @@ class HipSdfDecoder:
         bad, near_over = self._range_words(r)
         self._note_cluster_fault(r)
         f = lambda w: float(np.int32(r[w]).view(np.float32))
-        err, audit = f(19), f(35)
-        flips, evals = int(r[36]), int(r[37])
-        shell_picks, shell_pop, sumsq = int(r[39]), int(r[40]), f(41)
+        W = _native
+        err, audit = f(W.REC_STATUS + W.STATUS_MAX_ERR), f(W.REC_AUDIT_MAX_ERR)
+        flips, evals = int(r[W.REC_AUDIT_FLIPS]), int(r[W.REC_AUDIT_EVALS])
+        shell_picks, shell_pop, sumsq = int(r[W.REC_SHELL_PICKS]), int(r[W.REC_SHELL_POPULATION]), f(W.REC_AUDIT_SUMSQ)
         listed = max(int(r[w]) for w in cap_word)
         tail = self._tail_for(points, which) if points else self._tail
         est = audit * tail
@@ -777,9 +776,9 @@ class HipSdfDecoder:
             reason = "%d activations left the fp16 range" % bad
         elif listed > cap:
             reason = "%d voxels listed, capacity %d" % (listed, cap)
-        elif near_over or int(r[38]):
+        elif near_over or int(r[W.REC_NEAR_OVERFLOW]):
             reason = "near-level list overflowed"
-        elif int(r[18]):
+        elif int(r[W.REC_STATUS + W.STATUS_FIXUP]):
             reason, for_error = "a voxel taken as certainly negative was not", True
         elif flips:
             reason, for_error = "%d of %d audit voxels have the other sign" % (flips, evals), True
@@ -894,18 +893,17 @@ class HipSdfDecoder:
                 self.events["repeated_sweeps"] += 1
                 return False, None, False
             self.box_stats["exact"] += 1
-            b = r[:16].copy()
-            b[7] &= CLUSTER_FAULT_BIT - 1
-            b[15] &= CLUSTER_FAULT_BIT - 1
+            b = r[:_native.BOX_WORDS].copy()
+            b[list(_native.BOX_RANGE_WORDS)] &= _native.BOX_RANGE_MASK
             return True, b, False
         if ticket["epoch"] != self._recalibrations:
             ok, bad, reason = False, 0, "launched under activation scales that have been re-calibrated since"
         else:
-            ok, bad, _, reason = self._judge(r, ticket["tau"], self.box_stats, (32,), CAND_CAP, points=int(N) ** 3)
+            ok, bad, _, reason = self._judge(r, ticket["tau"], self.box_stats, (_native.REC_CANDIDATES,), CAND_CAP, points=int(N) ** 3)
         if ok:
             self.box_stats["box"] += 1
             self._box_failures = 0              # (three refusals IN A ROW switch the mode off)
-            return True, r[:16].copy(), False
+            return True, r[:_native.BOX_WORDS].copy(), False
         calibrate_allowance = True
         self.box_stats["fallback"] += 1
         self.events["repeated_sweeps"] += 1
@@ -953,8 +951,7 @@ class HipSdfDecoder:
             if ticket.get("recalibrate") and self._band_usable():
                 self._next_recal = "fine"           # the next periodic comparison measures a zoom lattice
         b = b.copy()
-        b[7] &= CLUSTER_FAULT_BIT - 1
-        b[15] &= CLUSTER_FAULT_BIT - 1
+        b[list(_native.BOX_RANGE_WORDS)] &= _native.BOX_RANGE_MASK
         return b
 
     # ---- both passes of a sample ENQUEUED in one go (round 5): the box-only coarse sweep, the zoom cube computed on
@@ -1075,7 +1072,7 @@ class HipSdfDecoder:
                 # the SAMPLE - refine_tau is absolute - and is honoured: the repeat runs on the fp32 chain.)
                 ok, bad, near_over, reason = False, 0, self._range_words(r)[1], "launched under activation scales that have been re-calibrated since"
             else:
-                ok, bad, near_over, reason = self._judge(r, ticket["tau"], self.band_stats, (33, 34), BAND_CAP, points=int(ticket["args"][0]) ** 3,
+                ok, bad, near_over, reason = self._judge(r, ticket["tau"], self.band_stats, (_native.REC_BAND, _native.REC_BAND + 1), BAND_CAP, points=int(ticket["args"][0]) ** 3,
                                                          which="fine")
             if ok:
                 self.band_stats["band"] += 1
@@ -1087,7 +1084,7 @@ class HipSdfDecoder:
                 self._recover(bad)
             else:
                 logging.warning("narrow-band fine sweep not accepted (%s): repeated as an ordinary sweep", reason)
-                if near_over or int(r[38]):
+                if near_over or int(r[_native.REC_NEAR_OVERFLOW]):
                     self._force_f32_once = True
                 elif ticket["epoch"] == self._recalibrations:
                     self._band_failures += 1

@@ -18,7 +18,7 @@ import time
 import numpy as np
 import torch
 
-from . import synthetic
+from . import _native, synthetic
 from .networks.model import build_decoder
 from .utils import mesh as mesh_utils
 
@@ -215,7 +215,7 @@ def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_c
             # waits for pass 1 (the zoom cube is data dependent); a coarse sweep whose guards fired (fp16 range, or the error
             # check of the box-only sweep) is repeated in there - the decoder is still bound to this sample
             b = hip.coarse_finish(ticket)
-        boxes = ([(b[0:3], b[3:6], int(b[6]))] if hb else []) + ([(b[8:11], b[11:14], int(b[14]))] if ob else [])
+        boxes = ([_native.box_of(b, 0)] if hb else []) + ([_native.box_of(b, 1)] if ob else [])
         nvs, norg = zoom_cube_from_bboxes(boxes, N, voxel)
         # the fine pass carries a guard record (fp16 range report; error check of the narrow-band sweep): read behind the
         # marching-cubes size read-back in surfaces().  The volumes go to marching cubes only (mc_only).

@@ -279,14 +279,14 @@ class TorchModuleDecoder:
             obj = obj and vo is not None
             bbox = None
             if want_bbox:
-                bbox = torch.empty(16, dtype=torch.int32, device=self.device)
-                tmp = torch.empty(16, dtype=torch.int32, device=self.device)
+                S = _native.BOX_STRIDE
+                bbox = torch.empty(_native.BOX_WORDS, dtype=torch.int32, device=self.device)
+                tmp = torch.empty(_native.BOX_WORDS, dtype=torch.int32, device=self.device)
                 for k, (on, vol) in enumerate(((hand, vh), (obj, vo))):
                     if on:
                         _native.check(L.asdf_neg_bbox(vol.data_ptr(), N, N, N, tmp.data_ptr(), stream), "asdf_neg_bbox")
-                        bbox[8 * k:8 * k + 8] = tmp[:8]
-                    else:
-                        bbox[8 * k:8 * k + 8] = torch.tensor([0x7fffffff] * 3 + [-1] * 3 + [0, 0], dtype=torch.int32, device=self.device)
-                bbox[7] = 0
-                bbox[15] = 0
+                        bbox[S * k:S * k + S] = tmp[:S]
+                    else:       # an empty box: min = INT_MAX, max = -1, count and range word 0
+                        bbox[S * k:S * k + S] = torch.tensor([0x7fffffff] * 3 + [-1] * 3 + [0, 0], dtype=torch.int32, device=self.device)
+                bbox[list(_native.BOX_RANGE_WORDS)] = 0
         return (vh if hand else None), (vo if obj else None), bbox

@@ -58,7 +58,7 @@ def get_higher_res_cube(hand_branch, obj_branch, sdf_values_hand, sdf_values_obj
     for on, vol in ((hand_branch, sdf_values_hand), (obj_branch, sdf_values_obj)):
         if on:
             b = neg_bbox(vol)
-            boxes.append((b[0:3], b[3:6], int(b[6])))
+            boxes.append(_native.box_of(b, 0))
     return zoom_cube_from_bboxes(boxes, N, voxel_size)
 
 
@@ -272,9 +272,9 @@ def decode_two_pass(hand_branch, obj_branch, decoder, latent_vec, mano_results, 
     b = hip.coarse_finish(hip.coarse_begin(N, [-1.0, -1.0, -1.0], voxel_size, mode, hand=hand_branch, obj=obj_branch))
     boxes = []
     if hand_branch:
-        boxes.append((b[0:3], b[3:6], int(b[6])))
+        boxes.append(_native.box_of(b, 0))
     if obj_branch:
-        boxes.append((b[8:11], b[11:14], int(b[14])))
+        boxes.append(_native.box_of(b, 1))
     new_voxel_size, new_origin = zoom_cube_from_bboxes(boxes, N, voxel_size)
     # fine pass: an ordinary sweep (range report through its bbox record), or - when the decoder is set to it and the caller
     # declares that the volumes go to marching cubes only - the narrow-band sweep; either is repeated if its guards fired

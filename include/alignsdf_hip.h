@@ -38,6 +38,51 @@ extern "C" {
 #define ASDF_GRID_REFERENCE 0 /* true-division indices exactly as utils/mesh.py:32-34 computes them */
 #define ASDF_GRID_INTEGER 1   /* floor-division indices (an axis-aligned lattice) */
 
+/* ---- Layout of the integer records the sweeps hand to their caller.  This table is the ONE definition: the kernels and the
+ * host code (alignsdf_amd/csrc) index the records through these names, alignsdf_amd/_native.py mirrors them for Python, and
+ * tests/test_record_layout.py pins every value.  All records are int32 words; "float bits" = the bit pattern of a non-negative
+ * fp32 value (ordered like the integer).
+ *
+ * BOX RECORD, int32[ASDF_BOX_WORDS]: one group of ASDF_BOX_STRIDE words per head (0 = hand, 1 = object). */
+#define ASDF_BOX_MIN 0                        /* [0..2] smallest index per axis of the negative voxels (INT_MAX when there is none) */
+#define ASDF_BOX_MAX 3                        /* [3..5] largest index per axis (-1 when there is none) */
+#define ASDF_BOX_COUNT 6                      /* negative voxels (one-plane sweeps: non-zero iff there is one) */
+#define ASDF_BOX_RANGE 7                      /* the range word: fp16 range violations of this head's sweep in the bits of
+                                                 ASDF_BOX_RANGE_MASK; head 0's word also carries the two flags below */
+#define ASDF_BOX_STRIDE 8
+#define ASDF_BOX_WORDS 16
+#define ASDF_BOX_CLUSTER_FAULT_BIT 0x20000000 /* bit 29: the cluster form of the short-list kernel reported a member that never arrived */
+#define ASDF_BOX_NEAR_OVERFLOW_BIT 0x40000000 /* bit 30: more near-level voxels than the refinement list holds */
+#define ASDF_BOX_RANGE_MASK 0x1fffffff        /* the count below the flags */
+/* STATUS RECORD of a decoder, int32[ASDF_STATUS_WORDS] (asdf_decoder_status; words not named here are reserved). */
+#define ASDF_STATUS_RANGE 0                   /* (point, lane-half) pairs that left the fp16 range in split-half / one-plane launches */
+#define ASDF_STATUS_LIST_OVERFLOW 1           /* voxels that did not fit the last sweep's re-evaluation list */
+#define ASDF_STATUS_FIXUP 2                   /* flag of the last re-evaluation: a voxel left the negative set */
+#define ASDF_STATUS_MAX_ERR 3                 /* largest |new - old| of the last re-evaluation (float bits) */
+#define ASDF_STATUS_PEAK 4                    /* [4 + ASDF_STATUS_PEAK_STRIDE m + l]: largest plane value x S_x of activation */
+#define ASDF_STATUS_PEAK_STRIDE 4             /*   vector h_l (l = 0..2) of MLP m (float bits): [4..6] and [8..10] */
+#define ASDF_STATUS_CLUSTER_FAULT 11          /* sticky: the cluster form reported a member that never arrived */
+#define ASDF_STATUS_CLOCK 12                  /* [12..13] / [14..15]: 64-bit shader-clock stamps of workgroup 0 at the first / last
+                                                 instruction of the last whole-lattice split-half or one-plane sweep */
+#define ASDF_STATUS_WORDS 16
+/* SWEEP RECORD of a one-plane sweep (asdf_decode_grid_box / _band), int32[ASDF_REC_WORDS]: the box record, a copy of the status
+ * record taken behind the call at ASDF_REC_STATUS, and the words below; [42..47] are zero. */
+#define ASDF_REC_STATUS 16
+#define ASDF_REC_CANDIDATES 32                /* box sweep: candidates (more than ASDF_CAND_CAP: not all were re-evaluated) */
+#define ASDF_REC_BAND 33                      /* [33] / [34] band sweep: voxels marked for the hand / object head (more than ASDF_BAND_CAP: ...) */
+#define ASDF_REC_AUDIT_MAX_ERR 35             /* largest |exact - one-plane| over the audit sample (float bits) */
+#define ASDF_REC_AUDIT_FLIPS 36               /* audit voxels whose sign the exact value contradicts */
+#define ASDF_REC_AUDIT_EVALS 37               /* audit evaluations (voxels x heads) */
+#define ASDF_REC_NEAR_OVERFLOW 38             /* near-level voxels beyond the refinement list (= status word ASDF_STATUS_LIST_OVERFLOW) */
+#define ASDF_REC_SHELL_PICKS 39               /* audit voxels drawn from the at-risk shell (tau <= |one-plane| < 2 tau) */
+#define ASDF_REC_SHELL_POPULATION 40          /* that shell's population (summed over the heads of a band sweep) */
+#define ASDF_REC_AUDIT_SUMSQ 41               /* sum of squared audit errors (fp32 bits): sigma = sqrt([41] / [37]) */
+#define ASDF_REC_WORDS 48
+/* Capacities of the voxel lists behind those counts. */
+#define ASDF_NEAR_CAP (1 << 16)               /* near-level refinement list of a split-half sweep */
+#define ASDF_CAND_CAP (1 << 21)               /* candidates of asdf_decode_grid_box */
+#define ASDF_BAND_CAP (1 << 22)               /* voxels per head asdf_decode_grid_band re-evaluates at most (25 % of 256^3) */
+
 typedef struct asdf_decoder asdf_decoder_t;
 
 /* Shape of the SDF MLP heads: networks/model.py:191-282 (SeparateDecoder.__init__) with
@@ -111,11 +156,11 @@ int asdf_decoder_set_sample_pixel(asdf_decoder_t* dec, const float* feat_dev, in
  *     coord[a] = idx[a] * voxel_size + origin[a]     (fp32 mul then add, a = 0,1,2; axis 2 fastest)
  * writing sdf_hand[N^3], sdf_obj[N^3] (device; either may be NULL - a SeparateDecoder head whose output is NULL is
  * not evaluated, and its bbox record stays empty) and, if bbox_dev != NULL, the
- * per-head bounding box of negative voxels as int32[16]:
+ * per-head bounding box of negative voxels as int32[16] (the BOX RECORD, ASDF_BOX_* above):
  *   [h*8 + 0..2] = min index per axis, [h*8 + 3..5] = max index per axis, [h*8 + 6] = #negative voxels,
- *   [h*8 + 7] = #points whose hidden activations left the fp16 range of the split-half planes (|x| >= 8188) - always
+ *   [h*8 + 7] = the range word: #points whose hidden activations left the fp16 range of the split-half planes (|x| >= 8188) - always
  *   0 under ASDF_MATH_F32; if non-zero under ASDF_MATH_F16X3 the caller should switch to ASDF_MATH_F32 and repeat.
- *   Bit 30 of word [7] is set when more voxels lay within the refinement threshold of the level than the refinement list
+ *   Bit 30 of word [7] (ASDF_BOX_NEAR_OVERFLOW_BIT) is set when more voxels lay within the refinement threshold of the level than the refinement list
  *   holds (asdf_decoder_set_refine): the signs next to the level are then the split-half arithmetic's, not the fp32 chain's.
  *   With bbox_dev == NULL the same count is available from asdf_decoder_status.
  * Replaces one pass of utils/mesh.py:27-63 (or :82-115) plus the nonzero/min/max of
@@ -131,13 +176,14 @@ int asdf_decode_grid(asdf_decoder_t* dec, int32_t N, const float origin[3], floa
  *   2. lists the voxels a head leaves undecided (-tau <= value < tau) that lie outside that head's box - only those can
  *      move it - and re-evaluates them on the fp32 MFMA chain (the arithmetic of ASDF_MATH_F32); every one that is
  *      negative extends the box.
- * bbox_dev (int32[48], required): words 0..15 then hold exactly the min / max words asdf_decode_grid would have produced,
+ * bbox_dev (int32[48], required; the SWEEP RECORD, ASDF_REC_* above): words 0..15 then hold exactly the min / max words asdf_decode_grid would have produced,
  * PROVIDED the one-plane values are within tau of the exact ones; word [6] / [14] is non-zero iff the head has a negative
  * voxel (it is not the count), [7] / [15] the fp16 range report as usual.  The proviso is checked on every call: on the
  * re-evaluated candidates, and on an AUDIT sample - asdf_decoder_set_audit voxels (default 65536) drawn at random from those
  * both heads decided by sign alone, re-evaluated with the split-half arithmetic of the ordinary sweep (at most half the lattice).  The outcome travels in
- * words 16..31, a copy of the decoder's status record taken behind the call ([16 + 3] = largest |exact - one-plane| over the
- * candidates (float bits), [16 + 2] != 0 = a voxel taken as certainly negative was not), and in words 32..39:
+ * words 16..31 (ASDF_REC_STATUS), a copy of the decoder's status record taken behind the call ([16 + 3] = largest |exact - one-plane| over the
+ * candidates (float bits), [16 + 2] != 0 = a voxel taken as certainly negative was not, [16 + 11] the cluster form's fault
+ * report), and in words 32..41:
  *   [32] number of candidates (more than 2^21: not all were re-evaluated),
  *   [33] / [34] asdf_decode_grid_band only: voxels marked for the hand / object head (more than 2^22: not all re-evaluated),
  *   [35] largest |exact - one-plane| over the audit sample (float bits), [36] audit voxels whose SIGN the exact value
@@ -287,7 +333,7 @@ int asdf_decoder_time_next_sweep(asdf_decoder_t* dec, void* event_start, void* e
 
 /* Range report of the split-half arithmetic that does NOT depend on a bbox buffer: every ASDF_MATH_F16X3 launch of this
  * decoder adds the number of (point, lane-half) pairs whose hidden activations left the fp16 range (or whose output is not
- * in [-1, 1]) to a device word the decoder owns.  Copies the record to out_host[16] ([0] = that count, [1] = near-level
+ * in [-1, 1]) to a device word the decoder owns.  Copies the record to out_host[16] (the STATUS RECORD, ASDF_STATUS_* above: [0] = that count, [1] = near-level
  * voxels (asdf_decode_grid_box: candidates) beyond the re-evaluation list's capacity, [2] = scratch flag of the last
  * re-evaluation (a voxel left the negative set), [3] = largest |new - old| value of the last re-evaluation (float bits), [4..6] / [8..10] = the largest fp16-plane value x S_x handed to the
  * conversion for the activation vectors h0 / h1 / h2 of MLP 0 / MLP 1, as float bit patterns, [12..13] / [14..15] = shader-clock stamps (s_memtime, 64 bit) of workgroup 0 at the first / last instruction of the
