@@ -8,7 +8,8 @@ reference lines it follows (paths relative to zerchen/AlignSDF).
 Pinning: tests/golden/ref_*.npz hold outputs of the reference itself (imported in the build
 container by tests/golden/make_ref_goldens.py); tests/test_oracle_decoder.py checks this module
 against them bit for bit (grid, zoom cube) or to 1e-6 (decoder outputs).  decode_points(..., dtype=torch.float64) runs the
-same chain in fp64: the truth the fp32-class GPU kernels are held to (tests/test_oracle_fp64.py, tests/test_gpu_split_half_fp64.py).
+same chain in fp64: the truth the fp32-class GPU kernels are held to (tests/test_oracle_fp64.py, tests/test_gpu_split_half_fp64.py);
+decode_points_pixel is the same for a PixelAlign sample (tests/test_oracle_pixel_align.py, tests/test_gpu_pixel_align_fp64.py).
 """
 import numpy as np
 import torch
@@ -203,6 +204,63 @@ def decode_points(state_dict, latent, xyz, specs, mano_results=None, obj_results
             sub = xyz[head:head + max_batch]
             feats = point_features(sub, specs, mano_results, obj_results)
             h, o = decode_sdf_multi_output(hp, op, latent, feats, specs)
+            hand[head:head + max_batch] = h.squeeze(1)
+            obj[head:head + max_batch] = o.squeeze(1)
+    return hand, obj
+
+
+def pixel_uv(xyz, cam_intr, root_joint, image_size, scale_factor):
+    """Projection of normalised points [M, 3] to grid_sample coordinates uv [M, 2] and the in-image mask, in xyz's dtype
+    (utils/utils.py:538-553): camera space = xyz * 2 / scale + root joint, cam_intr [3, 4] . (x, y, z, 1), xy / z, / ImageSize * 2 - 1,
+    inside = -1 <= u, v <= 1 inclusive (NaN / inf from z = 0 are outside)."""
+    xyz_cam = (xyz * 2 / scale_factor) + root_joint.reshape(1, 3)                           # :540
+    homo = torch.cat([xyz_cam, torch.ones(xyz.shape[0], 1, dtype=xyz.dtype)], 1)             # :542
+    xy_img = torch.matmul(cam_intr.reshape(3, 4), homo.t()).t()                              # :543
+    xy_img = xy_img[:, :2] / xy_img[:, 2:3]                                                  # :544
+    uv = xy_img / image_size * 2 - 1                                                         # :546
+    inside = (uv[:, 0] >= -1.0) & (uv[:, 0] <= 1.0) & (uv[:, 1] >= -1.0) & (uv[:, 1] <= 1.0)  # :550-553
+    return uv, inside
+
+
+def pixel_latent(feat, xyz, cam_intr, root_joint, image_size, scale_factor, inside=None):
+    """The per-point latent of a PixelAlign sample (utils/utils.py:536-558) in xyz's dtype: the bicubic sample (grid_sample,
+    align_corners, zero padding) of feat [1, C, H, W] at the point's projection, or feat.mean(3).mean(2) for a point outside the
+    image.  `inside` (bool [M]) replaces the in / out decision; the sample is still taken at this dtype's uv - grid_sample is defined
+    and continuous across |u| = 1, so a point that another precision's projection puts inside by an ulp has a well-defined value."""
+    uv, own = pixel_uv(xyz, cam_intr, root_joint, image_size, scale_factor)
+    mask = own if inside is None else torch.as_tensor(inside, dtype=torch.bool)
+    # (z = 0 gives NaN / inf: outside under either mask.  Beyond |u| = 3 every tap is outside the map or has weight 0: the sample is 0)
+    grid = torch.nan_to_num(uv, nan=-3.0, posinf=3.0, neginf=-3.0).clamp(-3.0, 3.0)
+    lat = F.grid_sample(feat, grid.reshape(1, -1, 1, 2), align_corners=True, mode="bicubic")[0, :, :, 0].t().clone()   # :548
+    lat[~mask] = feat.mean(3).mean(2)[0]                                                     # :554-556
+    return lat
+
+
+def decode_points_pixel(state_dict, feat, xyz, specs, mano_results, cam_intr, dtype=torch.float32, inside=None, max_batch=2 ** 15):
+    """decode_points for a PixelAlign sample (SeparateDecoder, xyz point features; utils/utils.py:561-572 with PixelAlign): the latent
+    of each point is pixel_latent of the feature map `feat` [1, C, H, W], the decoders are those of decode_points -> (hand [M],
+    obj [M]) of `dtype`.
+
+    dtype=torch.float64 runs projection, bicubic sample, channel mean, weight-norm fold and both decoders in fp64 on the stored
+    values.  `inside` (bool [M]) is the one exception: the in / out decision is taken from the caller - the fp32 op-for-op mask of the
+    kernel under test - so that a RIGHT fp32 decision at a borderline point costs nothing against this truth and a wrong one
+    costs the difference between the sampled latent and the channel mean."""
+    if specs["PointFeatSize"] != 3 or "lin0.bias" in state_dict:
+        raise ValueError("decode_points_pixel covers SeparateDecoder with xyz point features")
+    hp, op = effective_head_params(state_dict, "h", dtype), effective_head_params(state_dict, "o", dtype)
+    feat = torch.as_tensor(feat).to(dtype)
+    cam = torch.as_tensor(cam_intr).to(dtype)
+    root = torch.as_tensor(mano_results["joints"]).to(dtype).reshape(-1, 3)[0]
+    xyz = torch.as_tensor(xyz).to(dtype)
+    if inside is not None:
+        inside = torch.as_tensor(inside, dtype=torch.bool)
+    hand, obj = torch.zeros(xyz.shape[0], dtype=dtype), torch.zeros(xyz.shape[0], dtype=dtype)
+    with torch.no_grad():
+        for head in range(0, xyz.shape[0], max_batch):
+            sub = xyz[head:head + max_batch]
+            lat = pixel_latent(feat, sub, cam, root, specs["ImageSize"][0], specs["SdfScaleFactor"],
+                               None if inside is None else inside[head:head + max_batch])
+            h, o = separate_decoder(hp, op, torch.cat([lat, sub], 1), feat.shape[1], 3, specs["EncodeStyle"])   # :563-569
             hand[head:head + max_batch] = h.squeeze(1)
             obj[head:head + max_batch] = o.squeeze(1)
     return hand, obj
