@@ -7,17 +7,11 @@
 // Round 4: until then NeRF-encoded decoders ran ordinary sweeps on both passes.
 #include "k1_launch.h"
 #include "sdf_mlp_f16_kernel.h"
-#ifndef ASDF_NERF15_G
-#define ASDF_NERF15_G 2
-#endif
-#ifndef ASDF_NERF9_G
-#define ASDF_NERF9_G 2
-#endif
 
 namespace asdf {
 
-__global__ __launch_bounds__(256, 1) void sdf_mlp_f16p1_nerf9_kernel(const DecodeParams p) { sdf_mlp_f16_body<false, 0, 5, 1, ASDF_NERF9_G>(p); }
-__global__ __launch_bounds__(256, 1) void sdf_mlp_f16p1_nerf15_kernel(const DecodeParams p) { sdf_mlp_f16_body<false, 0, 8, 1, ASDF_NERF15_G>(p); }
+__global__ __launch_bounds__(256, 1) void sdf_mlp_f16p1_nerf9_kernel(const DecodeParams p) { sdf_mlp_f16_body<false, 0, 5, 1, 2>(p); }
+__global__ __launch_bounds__(256, 1) void sdf_mlp_f16p1_nerf15_kernel(const DecodeParams p) { sdf_mlp_f16_body<false, 0, 8, 1, 2>(p); }
 __global__ __launch_bounds__(256, 1) void sdf_mlp_f16p1_combined_nerf9_kernel(const DecodeParams p) { sdf_mlp_f16_body<true, 0, 5, 1, 1>(p); }
 __global__ __launch_bounds__(256, 1) void sdf_mlp_f16p1_combined_nerf15_kernel(const DecodeParams p) { sdf_mlp_f16_body<true, 0, 8, 1, 1>(p); }
 

@@ -40,14 +40,10 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #define ASDF_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 
-// relu(a0, a1) * mul -> one packed fp16 register (word `w` of an h8), as explicit 2-vectors: one v_pk_mul_f32 and one
-// v_cvt_pk_f16_f32 per pair (left to the SLP vectoriser the pairs came out shifted by one element, with a v_alignbit /
-// v_pack per register on top)
+// 2 relu(a0, a1) -> one packed fp16 register (word `w` of an h8), as explicit 2-vectors: one v_cvt_pk_f16_f32 per pair (left to
+// the SLP vectoriser the pairs came out shifted by one element, with a v_alignbit / v_pack per register on top)
 // (The one-plane kernels' own image - decoder.hip: rebuild_one_plane - is scaled so that an accumulator carries its activation's
-// plane scale: no multiply, and no running maximum either: ASDF16_P1_FOLD.)
-#ifndef ASDF16_P1_FOLD
-#define ASDF16_P1_FOLD 1
-#endif
+// plane scale: no multiply, and no running maximum either.)
 // The ReLU of the folded image must PRESERVE a poisoned value.  The matrix pipe's inf - inf is a NEGATIVE NaN (0xffc00000,
 // tools/trapsts_probe.hip), and an integer maximum against 0 - the cheapest ReLU - turns it (and a -inf) into a perfectly finite 0:
 // measured, a layer-2 overflow of 512 x the fp16 range reached the output as a finite value.  So: convert first, then
@@ -56,8 +52,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // the fp16 range stays non-finite through every layer, reaches the output as a NaN or exactly +-1, and is reported there.  The factor
 // 2 lives in the image's scales (decoder.hip: rebuild_one_plane carries S_x / 2 in the accumulators).  Three VALU instructions per
 // register pair (round 3: five, with a running maximum that the 512-register budget has no room for: +39 % time when it spills).
-__device__ __forceinline__ void relu_mul_pack(float a0, float a1, float mul, h8& dst, int w, float& amax) {
-#if ASDF16_P1_FOLD
+__device__ __forceinline__ void relu_pack(float a0, float a1, h8& dst, int w) {
   f32x2 raw;
   raw[0] = a0; raw[1] = a1;
   const h2 c = __builtin_convertvector(raw, h2);
@@ -66,98 +61,22 @@ __device__ __forceinline__ void relu_mul_pack(float a0, float a1, float mul, h8&
   u32x4 d0 = __builtin_bit_cast(u32x4, dst);
   d0[w] = __builtin_bit_cast(unsigned, r2);
   dst = __builtin_bit_cast(h8, d0);
-  return;
-#endif
-  f32x2 t;
-  t[0] = __int_as_float(max(__float_as_int(a0), 0));
-  t[1] = __int_as_float(max(__float_as_int(a1), 0));
-#if !ASDF16_P1_FOLD
-  t = t * mul;
-#ifndef ASDF16_NO_RANGE_CHECK
-  amax = fmaxf(amax, fmaxf(t[0], t[1]));
-  asm volatile("" : "+v"(amax));
-#endif
-#endif
-  const h2 r = __builtin_convertvector(t, h2);
-  u32x4 d = __builtin_bit_cast(u32x4, dst);
-  d[w] = __builtin_bit_cast(unsigned, r);
-  dst = __builtin_bit_cast(h8, d);
 }
 
 // wave64 maximum of a signed int on the DPP network (row_shr 1 / 2 / 4 / 8 inside the rows of 16 lanes, row_bcast:15 / :31 across them);
 // the result as a wave-uniform value (lane 63 holds it)
 __device__ __forceinline__ int wave_max_i32(int v) {
-#define ASDF16_DPP_MAX(ctrl, rows) v = max(v, __builtin_amdgcn_update_dpp((int)0x80000000, v, (ctrl), (rows), 0xf, false))
-  ASDF16_DPP_MAX(0x111, 0xf); ASDF16_DPP_MAX(0x112, 0xf); ASDF16_DPP_MAX(0x114, 0xf); ASDF16_DPP_MAX(0x118, 0xf);
-  ASDF16_DPP_MAX(0x142, 0xa); ASDF16_DPP_MAX(0x143, 0xc);
-#undef ASDF16_DPP_MAX
+#define ASDF_DPP_MAX(ctrl, rows) v = max(v, __builtin_amdgcn_update_dpp((int)0x80000000, v, (ctrl), (rows), 0xf, false))
+  ASDF_DPP_MAX(0x111, 0xf); ASDF_DPP_MAX(0x112, 0xf); ASDF_DPP_MAX(0x114, 0xf); ASDF_DPP_MAX(0x118, 0xf);
+  ASDF_DPP_MAX(0x142, 0xa); ASDF_DPP_MAX(0x143, 0xc);
+#undef ASDF_DPP_MAX
   return __builtin_amdgcn_readlane(v, 63);
 }
 
 constexpr float kActScaleDev = 8.0f;   // S_x (pack.h: kActScale)
 
-// schedule knobs (tools/k1h_ablate.hip sweeps them; the values here are the shipped ones)
 #ifndef ASDF16_STAGE_KB
 #define ASDF16_STAGE_KB 16       // K-blocks per stage: 16 = 32 KiB stages (one barrier per 48 MFMAs), 8 = 16 KiB stages
-#endif
-#ifndef ASDF16_SCHED_KB
-#define ASDF16_SCHED_KB 1        // a scheduling fence every this many K-blocks bounds how far A-fragment reads are hoisted
-#endif
-#ifndef ASDF16_PREFETCH
-#define ASDF16_PREFETCH 1        // A fragments are read from LDS this many K-blocks ahead of their MFMAs
-#endif
-#ifndef ASDF16_BARRIER_KB
-#define ASDF16_BARRIER_KB (ASDF16_STAGE_KB / 2)      // K-block in front of which the stage's wait + barrier sit
-#endif
-#ifndef ASDF16_BARRIER_KB_P1
-#define ASDF16_BARRIER_KB_P1 12      // ... of the one-plane kernel (16 KiB stages: the wait then covers pieces issued 2.75 stages ago)
-#endif
-#ifndef ASDF16_PRE_KB_P1
-#define ASDF16_PRE_KB_P1 (ASDF16_STAGE_KB / 2 + 2)      // ... and the K-block of its last stage that carries the next tile's preloads
-#endif
-#ifndef ASDF16_MFMA_ORDER
-#define ASDF16_MFMA_ORDER 0      // order of the three MFMAs of a K-block (an energy experiment: see the tuning log)
-#endif
-#ifndef ASDF16_LOADS_FIRST
-#define ASDF16_LOADS_FIRST 1     // a scheduling fence BEHIND the LDS reads of a K-block: they issue ahead of its MFMAs (the
-#endif                           // compiler otherwise sinks them to one MFMA in front of their first use)
-#ifndef ASDF16_PRELOAD
-#define ASDF16_PRELOAD 1         // biases / point fragments / w4 of the NEXT tile are read half a tile ahead
-#endif
-#ifndef ASDF16_PIN_ACC
-#define ASDF16_PIN_ACC 1         // deferred epilogues read the finished accumulator part by part (no up-front copy)
-#endif
-#ifndef ASDF16_L0_PIPE
-#define ASDF16_L0_PIPE 1         // one-plane kernel: layer 0 software-pipelined over all 16 tiles in front of layer 1
-#endif
-#ifndef ASDF16_PRE_KB
-#define ASDF16_PRE_KB (ASDF16_STAGE_KB / 2 + 2)      // K-block of a tile's last stage whose region carries the next tile's preloads
-#endif
-// one-plane kernel (PL = 1) only - its K-blocks are 32 / 64 matrix-pipe cycles, not 96, so what hides behind a K-block of the
-// split-half kernel does not hide here:
-#ifndef ASDF16_P1_FP16PT
-#define ASDF16_P1_FP16PT 1       // point features and bias rows of layers 0 / 2 on ONE fp16 MFMA per tile (sdf_layout.h: kA16Floats)
-#endif
-#ifndef ASDF16_W4_TILE
-#define ASDF16_W4_TILE 1         // the 16 last-layer weights of a tile's deferred epilogue read at once, half a tile ahead (not pair by pair one K-block ahead)
-#endif
-#ifndef ASDF16_PF_G2
-#define ASDF16_PF_G2 2           // A-fragment prefetch distance (K-blocks of 64 cycles) of the two-group kernel
-#endif
-#ifndef ASDF16_FOLD_BALLOT
-#define ASDF16_FOLD_BALLOT 1     // the negative-voxel fold of a tile is skipped when no lane of the wave has anything to fold
-#endif
-#ifndef ASDF16_MIX_SPLIT
-#define ASDF16_MIX_SPLIT 1       // split-half kernel: the plane split on v_fma_mix{lo,hi}_f16 (9 instead of 17 VALU instructions per epilogue part)
-#endif
-#ifndef ASDF16_EPI_STEPS
-#define ASDF16_EPI_STEPS 1       // split-half kernel: a deferred epilogue part is issued in three pieces, one behind each MFMA of its K-block
-#endif
-#ifndef ASDF16_DMA_PER_KB
-#define ASDF16_DMA_PER_KB 1      // split-half kernel: ONE LDS-DMA piece per K-block (behind its last MFMA) over K-blocks BARRIER_KB .. + 7, not three per K-block
-#endif
-#ifndef ASDF16_FAST_TANH
-#define ASDF16_FAST_TANH 1       // tanh as 1 - 2 / (1 + exp(2 x)) on the hardware exp / rcp (absolute error ~1e-7; the values carry ~1e-4)
 #endif
 
 // The split-half stream of a head is a flat sequence of (tile, K-block) records of 2 KiB ([plane hi / lo][lane][8 halves]),
@@ -182,8 +101,8 @@ struct S16 {
   static constexpr int kRingFloats = kRing * kFloats;
   static constexpr int kMfmas = PL == 2 ? 3 : G;           // MFMAs per K-block
   // A fragments are read from LDS this many K-blocks ahead of their MFMAs: the read latency (~100 cycles) has to fit in the
-  // MFMA time of that distance - one K-block of three MFMAs (96 cycles), or three K-blocks of one
-  static constexpr int kPrefetch = PL == 2 ? ASDF16_PREFETCH : (G == 2 ? ASDF16_PF_G2 : 3) * ASDF16_PREFETCH;
+  // MFMA time of that distance - one K-block of three MFMAs (96 cycles), three K-blocks of one, or two K-blocks of two (64 cycles each)
+  static constexpr int kPrefetch = PL == 2 ? 1 : (G == 2 ? 2 : 3);
   static_assert(PL == 2 ? G == 1 : (G == 1 || G == 2), "point groups");
   static_assert(kPieces == 4 || kPieces == 8, "stage size");
 };
@@ -193,7 +112,9 @@ constexpr int kS16WaveFloats = S16<2>::kWaveFloats;
 constexpr int kRing16Floats = S16<2>::kRingFloats;
 // LDS: ring + constants + two 8-int negative-voxel records per wave (the register file has no room for per-lane ones)
 constexpr int kWrecInts = 20;    // per wave: two 8-int negative-voxel records + the largest plane value of layers 0..2 (+ pad)
-constexpr bool pt16(int kp, int planes) { return ASDF16_P1_FP16PT && planes == 1 && kp == 2; }
+// one-plane kernel (its K-blocks are 32 / 64 matrix-pipe cycles, not 96, so what hides behind a K-block of the split-half kernel does
+// not hide there): point features and bias rows of layers 0 / 2 on ONE fp16 MFMA per tile (sdf_layout.h: kA16Floats)
+constexpr bool pt16(int kp, int planes) { return planes == 1 && kp == 2; }
 constexpr int lds_bytes_f16(int kp, int planes = 2) {
   return (kRing * kS16Kb * 256 * planes + cst_offsets(kp).floats + (pt16(kp, planes) ? kA16Floats : 0)) * 4 + kWaves * kWrecInts * 4;
 }
@@ -208,12 +129,12 @@ template <int PL = 2, int G = 1, bool MIX = false>
 __device__ __forceinline__ void split_part(const f32x16& acc, const f32x16& accb, float mul, h8& hi0, h8& lo0, h8& hi1, h8& lo1, float& amax,
                                            int e, int g = -1, int step = -1, float* rr = nullptr) {
   if (PL == 1 && G == 2 && g != 0)         // the second point group: its planes live where the low planes of the split-half kernel do
-    relu_mul_pack(accb[2 * e], accb[2 * e + 1], mul, e < 4 ? lo0 : lo1, e & 3, amax);
+    relu_pack(accb[2 * e], accb[2 * e + 1], e < 4 ? lo0 : lo1, e & 3);
   if (PL == 1 && G == 2 && g == 1) return;
   if (PL == 1) {
     // one plane: part e converts the NEIGHBOURING accumulator registers 2 e, 2 e + 1 (both land in one packed fp16 register,
     // one v_cvt_pk), about 5 VALU instructions - a part has to fit the shadow of the ONE MFMA of its K-block here
-    relu_mul_pack(acc[2 * e], acc[2 * e + 1], mul, e < 4 ? hi0 : hi1, e & 3, amax);
+    relu_pack(acc[2 * e], acc[2 * e + 1], e < 4 ? hi0 : hi1, e & 3);
     return;
   }
   if (MIX) {
@@ -242,21 +163,16 @@ __device__ __forceinline__ void split_part(const f32x16& acc, const f32x16& accb
     unsigned a = H0[e >> 1], b = L0[e >> 1], c = H1[e >> 1], d = L1[e >> 1];
     // the two high planes, the running maximum behind them, then the low planes (a half-register write needs two wait states in
     // front of its first read: the maximum and the sibling's instruction are those two)
-#ifndef ASDF16_NO_RANGE_CHECK
-#define ASDF16_AMAX_LINE "v_max3_f32 %2, %2, %3, %4\n\t"
-#else
-#define ASDF16_AMAX_LINE "s_nop 0\n\t"
-#endif
     if (step != 2) {
       if (e & 1)
         asm("v_fma_mixhi_f16 %0, %3, %5, 0\n\t"
             "v_fma_mixhi_f16 %1, %4, %5, 0\n\t"
-            ASDF16_AMAX_LINE
+            "v_max3_f32 %2, %2, %3, %4\n\t"
             : "+v"(a), "+v"(c), "+v"(amax) : "v"(r0), "v"(r1), "v"(mul));
       else        // (the even element defines the register: nothing of the previous tile's value is read)
         asm("v_fma_mixlo_f16 %0, %3, %5, 0\n\t"
             "v_fma_mixlo_f16 %1, %4, %5, 0\n\t"
-            ASDF16_AMAX_LINE
+            "v_max3_f32 %2, %2, %3, %4\n\t"
             : "=&v"(a), "=&v"(c), "+v"(amax) : "v"(r0), "v"(r1), "v"(mul));
       H0[e >> 1] = a; H1[e >> 1] = c;
       hi0 = __builtin_bit_cast(h8, H0); hi1 = __builtin_bit_cast(h8, H1);
@@ -273,15 +189,12 @@ __device__ __forceinline__ void split_part(const f32x16& acc, const f32x16& accb
       L0[e >> 1] = b; L1[e >> 1] = d;
       lo0 = __builtin_bit_cast(h8, L0); lo1 = __builtin_bit_cast(h8, L1);
     }
-#undef ASDF16_AMAX_LINE
     return;
   }
   }
   const float t0 = __int_as_float(max(__float_as_int(acc[e]), 0)) * mul;
   const float t1 = __int_as_float(max(__float_as_int(acc[8 + e]), 0)) * mul;
-#ifndef ASDF16_NO_RANGE_CHECK
   amax = fmaxf(amax, fmaxf(t0, t1));
-#endif
   const _Float16 a = (_Float16)t0, b = (_Float16)t1;
   hi0[e] = a;
   hi1[e] = b;
@@ -289,9 +202,7 @@ __device__ __forceinline__ void split_part(const f32x16& acc, const f32x16& accb
     lo0[e] = (_Float16)(t0 - (float)a);
     lo1[e] = (_Float16)(t1 - (float)b);
   }
-#ifndef ASDF16_NO_RANGE_CHECK
   asm volatile("" : "+v"(amax));      // keep the running maximum where it is computed (see dot_w4's pin in sdf_mlp_kernel.h)
-#endif
 }
 
 template <int PL = 2, int G = 1, bool MIX = false>
@@ -305,11 +216,8 @@ __device__ __forceinline__ void split_tile(const f32x16& acc, const f32x16& accb
 constexpr int kEpiChunks = 8;
 // ... starting at this K-block: the accumulator the epilogue reads was finished by the MFMA right in front of the stage,
 // and an AGPR read within ~3 MFMAs of it waits for the matrix pipe (s_nop + dependency stall)
-#ifndef ASDF16_EPI_SHIFT
-#define ASDF16_EPI_SHIFT (ASDF16_STAGE_KB > 8 ? 1 : 0)
-#endif
-constexpr int kEpiShift = ASDF16_EPI_SHIFT;
-static_assert(kEpiShift + kEpiChunks <= ASDF16_STAGE_KB, "epilogue slots");
+constexpr int kEpiShift = kS16Kb > 8 ? 1 : 0;
+static_assert(kEpiShift + kEpiChunks <= kS16Kb, "epilogue slots");
 struct NoOp16 {
   __device__ __forceinline__ void operator()(int, int = -1) const {}
 };
@@ -319,13 +227,10 @@ typedef NoOp16 NoEpilogue16;
 // in front of it (instruction selection otherwise copies a whole finished accumulator out of the AGPRs right behind its
 // last MFMA - an s_nop 11 plus the wait for that MFMA at every tile boundary)
 // (One-plane kernel with two point groups: the pin does the opposite there - with it the register allocator copies every finished
-// layer-3 accumulator out of the AGPRs and back in, 64 moves and two s_nop 11 per tile; ASDF16_PIN_ACC_P1 = 0.)
-#ifndef ASDF16_PIN_ACC_P1
-#define ASDF16_PIN_ACC_P1 0
-#endif
+// layer-3 accumulator out of the AGPRs and back in, 64 moves and two s_nop 11 per tile: the one-plane kernels do not pin.)
 template <int PL = 2>
 __device__ __forceinline__ void pin_acc(f32x16& acc) {
-  if (PL == 2 ? ASDF16_PIN_ACC : ASDF16_PIN_ACC_P1) asm volatile("" : "+a"(acc));
+  if (PL == 2) asm volatile("" : "+a"(acc));
 }
 
 // One LDS-DMA piece (1 KiB per wave) of the wave's share of a stage; P is the piece index.
@@ -336,6 +241,11 @@ __device__ __forceinline__ void dma_piece(const float* src, unsigned dst) {
   lds_dma16_off<(P & 3) * 1024>(src + (P >> 2) * 1024, dst + (P >> 2) * 4096);
 }
 
+// K-block in front of which a stage's wait + barrier sit; the LDS-DMA pieces of the refill follow it
+constexpr int kBarrierKb = kS16Kb / 2;
+constexpr int kBarrierKbP1 = 12;      // ... of the one-plane kernel (16 KiB stages: the wait then covers pieces issued 2.75 stages ago)
+// K-block of a tile's last stage whose region carries the next tile's preloads (biases / point fragments / w4: read half a tile ahead)
+constexpr int kPreKb = kS16Kb / 2 + 2;
 
 // One stage = kS16Kb K-blocks of one 32-row output tile: [kblock][plane hi / lo][lane][8 halves].
 // On entry (ah[i], al[i]) hold the A fragments of K-blocks 0 .. PREFETCH-1 of THIS stage; on exit those of the next
@@ -352,7 +262,7 @@ __device__ __forceinline__ void stage16(f32x16& acc, f32x16& accb, const h8 (&xh
                                         const float* next_src, unsigned lds_ring_base, int lane, int wave,
                                         h8 (&ah)[S16<PL, G>::kPrefetch], h8 (&al)[S16<PL, G>::kPrefetch], Pre&& pre, Epi&& epi) {
   constexpr int PF = S16<PL, G>::kPrefetch;
-  constexpr int BKB = PL == 2 ? ASDF16_BARRIER_KB : ASDF16_BARRIER_KB_P1;
+  constexpr int BKB = PL == 2 ? kBarrierKb : kBarrierKbP1;
   constexpr int nslot = (SLOT + kRing - 1) % kRing;   // slot of stage (this - 1), refilled with stage (this + 3)
   using SG = S16<PL, G>;
   const float* src = next_src + wave * SG::kWaveFloats + lane * 4;
@@ -373,28 +283,17 @@ __device__ __forceinline__ void stage16(f32x16& acc, f32x16& accb, const h8 (&xh
     bufh[kb + PF] = kb + PF < kS16Kb ? cur[((kb + PF) * PL + 0) * 64] : nxt[((kb + PF - kS16Kb) * PL + 0) * 64];
     if (PL == 2) bufl[kb + PF] = kb + PF < kS16Kb ? cur[((kb + PF) * 2 + 1) * 64] : nxt[((kb + PF - kS16Kb) * 2 + 1) * 64];
     pre(kb);
-#if ASDF16_LOADS_FIRST
     __builtin_amdgcn_sched_barrier(0);
-#endif
     constexpr int base = Q * kS16Kb;
 #pragma unroll
     for (int j = 0; j < SG::kMfmas; ++j) {
       if (PL == 1 && j == 0) acc = ASDF_MFMA16(bufh[kb], xh[base + kb], acc);
       else if (PL == 1) accb = ASDF_MFMA16(bufh[kb], xl[base + kb], accb);       // the second point group, same A fragment
-      else
-#if ASDF16_MFMA_ORDER == 0
-      // W_hi . x_lo, W_lo . x_hi, W_hi . x_hi - small terms first
-      acc = ASDF_MFMA16(j == 1 ? bufl[kb] : bufh[kb], j == 0 ? xl[base + kb] : xh[base + kb], acc);
-#elif ASDF16_MFMA_ORDER == 1
-      // W_hi . x_lo, W_hi . x_hi, W_lo . x_hi - consecutive MFMAs share an operand
-      acc = ASDF_MFMA16(j == 2 ? bufl[kb] : bufh[kb], j == 0 ? xl[base + kb] : xh[base + kb], acc);
-#else
-      // W_lo . x_hi, W_hi . x_hi, W_hi . x_lo
-      acc = ASDF_MFMA16(j == 0 ? bufl[kb] : bufh[kb], j == 2 ? xl[base + kb] : xh[base + kb], acc);
-#endif
+      else      // W_hi . x_lo, W_lo . x_hi, W_hi . x_hi - small terms first
+        acc = ASDF_MFMA16(j == 1 ? bufl[kb] : bufh[kb], j == 0 ? xl[base + kb] : xh[base + kb], acc);
       // one DMA piece per MFMA shadow behind the barrier; split-half kernel (round 5): one per K-block, behind its LAST MFMA - the
       // gap that carries the least of a deferred epilogue part
-      constexpr bool kDmaPerKb = STEPS && ASDF16_DMA_PER_KB && kS16Kb - BKB >= SG::kPieces;
+      constexpr bool kDmaPerKb = STEPS && kS16Kb - BKB >= SG::kPieces;
       const int m = kDmaPerKb ? (j == 2 ? kb - BKB : -1) : (kb - BKB) * SG::kMfmas + j;
       if (!(ABL & 1) && !(ABL & 32) && m >= 0 && m < SG::kPieces) {
         if (m == 0) dma_piece<0>(src, dst);
@@ -407,9 +306,6 @@ __device__ __forceinline__ void stage16(f32x16& acc, f32x16& accb, const h8 (&xh
         else dma_piece<7>(src, dst);
         __builtin_amdgcn_sched_barrier(0);
       }
-#ifdef ASDF16_FENCE_EVERY_MFMA
-      __builtin_amdgcn_sched_barrier(0);
-#endif
       if (PL == 1 && G == 2) {
         // two point groups: each group's share of the deferred epilogue goes behind ONE of the two MFMAs (left to itself the
         // scheduler issues both MFMAs back to back - the second waits a whole MFMA for the pipe - and then all the VALU work)
@@ -428,19 +324,11 @@ __device__ __forceinline__ void stage16(f32x16& acc, f32x16& accb, const h8 (&xh
     }
     if (!((PL == 1 && G == 2) || STEPS)) epi(kb);
     // K-block = scheduling region (hoisted, 16 K-blocks of A fragments do not fit the register file either)
-    if (ASDF16_LOADS_FIRST || (kS16Kb > 8 && (kb % ASDF16_SCHED_KB) == ASDF16_SCHED_KB - 1)) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
   for (int i = 0; i < PF; ++i) { ah[i] = bufh[kS16Kb + i]; if (PL == 2) al[i] = bufl[kS16Kb + i]; }
 }
-
-// Timing instrumentation of tools/k1h_ablate.hip (-DASDF16_SEGMENT_TIMES): shader-clock stamps of wave 0 of workgroup 0 at
-// the layer boundaries of its third tile of MLP 0 go to g_seg[] (declared by the tool).  Not compiled into the product.
-#ifdef ASDF16_SEGMENT_TIMES
-#define ASDF16_MARK(k) do { __builtin_amdgcn_sched_barrier(0); seg_t[k] = clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define ASDF16_MARK(k) do { } while (0)
-#endif
 
 // p.stream / p.cst are the split-half images here (pack_decoder_f16).  KP = K-steps of the point features on the fp32
 // MFMA in layers 0 and 2: 2 = affine xyz, 5 / 8 = NeRF encoding of 9 / 15 features (those need 16 KiB stages: their
@@ -457,8 +345,8 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
   // forms only: the CombinedDecoder forms sit at the register limit with their second dot product - the asm blocks' simultaneous
   // destinations cost them 20 .. 48 B of scratch, and with the pieces their unrolled layer-3 loop exceeds the compiler's full-unroll
   // budget and comes out ROLLED, with indexed registers - and keep the round-2 form (same bits).
-  constexpr bool kMix = ASDF16_MIX_SPLIT && PL == 2 && !TWO_OUT;
-  constexpr bool kSteps = ASDF16_EPI_STEPS && kMix;
+  constexpr bool kMix = PL == 2 && !TWO_OUT;
+  constexpr bool kSteps = kMix;      // (the pieces exist only in the mix form of split_part)
   static_assert(lds_bytes_f16(KP, PL) <= 160 * 1024, "LDS budget");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* ring = smem;
@@ -502,7 +390,6 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
     }
     // (one-plane kernels: the fp16 point-feature / bias operands of layers 0 and 2, behind the per-wave records)
     constexpr bool kPt16 = pt16(KP, PL);
-    static_assert(!kPt16 || ASDF16_L0_PIPE, "the fp16 point operands are wired into the pipelined layer 0");
     float* a16s = cst + CL::kFloats + kWaves * kWrecInts;
     if (kPt16) {
       const f32x4* src4 = reinterpret_cast<const f32x4*>(p.a16 + (size_t)head * kA16Floats);
@@ -536,10 +423,6 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
 
 #pragma unroll 1
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-#ifdef ASDF16_SEGMENT_TIMES
-      long long seg_t[8];
-#endif
-      ASDF16_MARK(0);
       const long long pi = tile * kTilePts + wave * (kWavePts * G) + (lane & 31);
       const bool valid = pi < npts;
       const long long po = SUB ? (valid ? (long long)p.idx[pi] : 0) : pi;      // where the point lives in the lattice / the outputs
@@ -599,7 +482,6 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
         }
         return r;
       };
-      ASDF16_MARK(7);      // (coordinates done)
       const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       h8 bq0, bq0b;
       if (kPt16) {
@@ -623,8 +505,7 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
       float pf2[KP];                            // A fragments (fp32 MFMA) of the next layer-2 tile
       float w4c[2], w4n[2], w4bc[2], w4bn[2];   // last-layer weights of the current / next part of the layer-3 epilogue
       // one-plane kernel: all 16 of a tile's, read half a tile ahead (a K-block of 64 cycles is shorter than the LDS latency)
-      constexpr bool kW4Tile = ASDF16_W4_TILE && PL == 1 && !TWO_OUT;
-      constexpr int kPreKb = PL == 2 ? ASDF16_PRE_KB : ASDF16_PRE_KB_P1;
+      constexpr bool kW4Tile = PL == 1 && !TWO_OUT;
       // layer 2 has ONE stage per tile: the preload of the next tile's bias row lands in the accumulator the deferred epilogue of
       // the previous tile is still reading until its last part (K-block kEpiShift + kEpiChunks - 1)
       static_assert(kS16Kb == 8 || kPreKb >= kEpiShift + kEpiChunks, "preload K-block inside the epilogue slots");
@@ -671,8 +552,8 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
       // the split of a tile is ~100 VALU instructions against 128 cycles of fp32 MFMA: layer 0 is VALU-bound when it runs
       // on its own.  Only the tiles the first stage of layer 1 consumes (K-blocks 0 .. kS16Kb-1) are computed up front;
       // the others ride in the epilogue slots of that stage, under its fp16 MFMAs.
-      constexpr int kL0Front = (PL == 1 && ASDF16_L0_PIPE) ? kTilesHidden : (kS16Kb / 2 < kEpiChunks ? kTilesHidden : kS16Kb / 2);
-      if (PL == 1 && ASDF16_L0_PIPE) {
+      constexpr int kL0Front = PL == 1 ? kTilesHidden : (kS16Kb / 2 < kEpiChunks ? kTilesHidden : kS16Kb / 2);
+      if (PL == 1) {
         // One-plane kernel: all 16 tiles up front, software-pipelined over three accumulator sets - the bias / fragment reads
         // of tile t + 2, then the fp32 MFMAs of tile t + 1, then the fp16 conversions of tile t.  (Tile by tile, and with the
         // second half squeezed into the 64-cycle K-blocks of layer 1's first stage, layer 0 took 21.6 k of this kernel's
@@ -720,17 +601,15 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
       if (G == 2) acc1b[0] = acc1[0];
 #pragma unroll
       for (int t = 0; t < kL0Front; ++t) {
-        if (ASDF16_PRELOAD && t + 1 < kTilesHidden) { l0_load(t + 1); __builtin_amdgcn_sched_barrier(0); }
+        if (t + 1 < kTilesHidden) { l0_load(t + 1); __builtin_amdgcn_sched_barrier(0); }
         l0_compute(t);
-        if (!ASDF16_PRELOAD && t + 1 < kTilesHidden) l0_load(t + 1);
-        if (ASDF16_PRELOAD) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
       }
       }
 
 #define ASDF_STAGE16(KB, Q, SLOT, ACC, XH, XL, SIDX, PRE, EPI) \
   stage16<KB, Q, SLOT, ABL, PL, G, kSteps>(ACC, ACC##b, XH, XL, ring, src_of((SIDX) + 3), lds_ring_base, lane, wave, ah, al, PRE, EPI)
 
-      ASDF16_MARK(1);
       // (split-half kernel: the second argument of an epilogue callback is the PIECE of the part - stage16 calls it behind each of
       // the K-block's three MFMAs - and `er` carries a part's two ReLUs from piece to piece)
       float er[2] = {0.0f, 0.0f};
@@ -741,10 +620,9 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
       for (int t = 0; t < kTilesL1; ++t) {
         f32x16& acc = acc1[t & 1];
         f32x16& accb = (G == 2 ? acc1b : acc1)[t & 1];
-        if (!ASDF16_PRELOAD && t > 0) acc = load_bias16(hc + CL::kB1 + (t * 2 + half) * 16);
         auto pre = [&](int kb) {       // first stage: the layer-0 tile of the NEXT K-block's epilogue slot
           const int c = kb - kEpiShift;
-          if (t == 0 && ASDF16_PRELOAD && kL0Front < kTilesHidden && c >= 0 && c + 1 < kEpiChunks) l0_load(kL0Front + c + 1);
+          if (t == 0 && kL0Front < kTilesHidden && c >= 0 && c + 1 < kEpiChunks) l0_load(kL0Front + c + 1);
         };
         auto epi = [&](int kb, int g = -1) {
           const int c = kb - kEpiShift;
@@ -763,10 +641,7 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
               return;
             }
             if (kSteps && g > 0) return;
-            if (kL0Front < kTilesHidden) {       // layer-0 tiles 8 .. 15: consumed by the next stage
-              l0_compute(kL0Front + c, kSteps ? -1 : g);
-              if (!ASDF16_PRELOAD && c + 1 < kEpiChunks) l0_load(kL0Front + c + 1);
-            }
+            if (kL0Front < kTilesHidden) l0_compute(kL0Front + c, kSteps ? -1 : g);       // layer-0 tiles 8 .. 15: consumed by the next stage
             return;
           }
           if (ABL & 4) { asm volatile("" :: "v"(acc1[(t - 1) & 1])); return; }
@@ -776,7 +651,7 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
                             h1l[2 * (t - 1) + 1], amax1, c, kSteps ? -1 : g, kSteps ? g : -1, er);
         };
         auto pre_last = [&](int c) {   // last stage: bias row (and point fragments) of the next tile
-          if (!ASDF16_PRELOAD || c != kPreKb) return;
+          if (c != kPreKb) return;
           if (t + 1 < kTilesL1) { acc1[(t + 1) & 1] = load_bias16(hc + CL::kB1 + ((t + 1) * 2 + half) * 16); if (G == 2) acc1b[(t + 1) & 1] = acc1[(t + 1) & 1]; }
           else { acc2[0] = load_bias16(hc + CL::kC2 + half * 16); if (G == 2) acc2b[0] = acc2[0]; load_pf2(0); }
         };
@@ -796,7 +671,6 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
 #endif
       }
 
-      ASDF16_MARK(2);
       // ---- layer 2: [h1 (256) | xyz (4, fp32 MFMA, pre-scaled A fragments)] -> 512
       h8 h2h[2 * kTilesHidden], h2l[2 * kTilesHidden];
       if (ABL & 4) for (int t = 0; t < 2 * kTilesHidden; ++t) { h2h[t] = h0h[t]; h2l[t] = h0l[t]; }
@@ -805,7 +679,6 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
         constexpr int SLOT = decltype(slot_tag)::value;
         f32x16& acc = acc2[t & 1];
         f32x16& accb = (G == 2 ? acc2b : acc2)[t & 1];
-        if (!ASDF16_PRELOAD) { acc = load_bias16(hc + CL::kC2 + (t * 2 + half) * 16); load_pf2(t); }
 #pragma unroll
         for (int s = 0; s < KP; ++s) {
           const float af = kPreloadPf ? pf2[s] : hc[CL::kA2 + (t * KP + s) * 64 + lane];
@@ -829,7 +702,7 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
           }
         };
         auto pre_last = [&](int c) {
-          if (!ASDF16_PRELOAD || c != kPreKb) return;
+          if (c != kPreKb) return;
           if (t + 1 < kTilesHidden) {
             acc2[(t + 1) & 1] = load_bias16(hc + CL::kC2 + ((t + 1) * 2 + half) * 16);
             if (G == 2) acc2b[(t + 1) & 1] = acc2[(t + 1) & 1];
@@ -862,7 +735,6 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
 #endif
       }
 
-      ASDF16_MARK(3);
       // ---- layer 3 (512 -> 512) fused with layer 4 (dot with w4 / (S_w3 S_x)) and tanh
       float part = 0.0f, partb = 0.0f, partg = 0.0f;      // partg: the second point group's dot product (G == 2)
       // accumulator registers 2 c, 2 c + 1 of a finished tile into the last-layer dot product(s), weights from (w4c, w4bc)
@@ -871,7 +743,7 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
         for (int r = 0; r < 2; ++r) {
           if (only >= 0 && only != r) continue;
           const float w = kW4Tile ? w4t[2 * c + r] : w4c[r];
-          if (PL == 1 && ASDF16_P1_FOLD) {
+          if (PL == 1) {
             // relu(a) w = a (w / 2) + |a| (w / 2): two FMAs like max + FMA, and a NaN / infinity of either sign stays one (the image's
             // last-layer weights carry the 1 / 2)
             if (g != 1) {
@@ -896,7 +768,6 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
       for (int t = 0; t < kTilesHidden; ++t) {
         f32x16& acc = acc3[t & 1];
         f32x16& accb = (G == 2 ? acc3b : acc3)[t & 1];
-        if (!ASDF16_PRELOAD) acc = load_bias16(hc + CL::kB3 + (t * 2 + half) * 16);
         auto pre = [&](int kb) {       // first stage: w4 of the next epilogue part
           const int c = kb - kEpiShift;
           if (!kW4Tile && t > 0 && c >= 0 && c + 1 < kEpiChunks) load_w4(t - 1, c + 1);
@@ -925,7 +796,7 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
         };
         auto pre_last = [&](int c) {   // last stage: bias row of the next tile, w4 of the first part of this tile's epilogue
           if (c != kPreKb) return;
-          if (ASDF16_PRELOAD && t + 1 < kTilesHidden) {
+          if (t + 1 < kTilesHidden) {
             acc3[(t + 1) & 1] = load_bias16(hc + CL::kB3 + ((t + 1) * 2 + half) * 16);
             if (G == 2) acc3b[(t + 1) & 1] = acc3[(t + 1) & 1];
           }
@@ -949,7 +820,6 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
         }
 #endif
       }
-      ASDF16_MARK(4);
       // the last tile's epilogue has no MFMA stream to hide under
 #pragma unroll
       for (int c = 0; c < kEpiChunks; ++c) {
@@ -959,9 +829,8 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
       }
 #undef ASDF_STAGE16
       auto tanh_out = [&](float x) -> float {
-#if ASDF16_FAST_TANH
+        // one plane: 1 - 2 / (1 + exp(2 x)) on the hardware exp / rcp (absolute error ~1e-7; the values carry ~1e-4)
         if (PL == 1) return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x));
-#endif
         return tanhf(x);
       };
       part += __shfl_xor(part, 32);
@@ -1032,7 +901,7 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
       // fp16 range arrives HERE as a non-finite PRE-activation of the tanh: a NaN, or an infinity.  The check is on that value, not
       // on the output - tanhf returns exactly +-1 for every finite argument beyond ~9, so a decoder that merely saturates in the far
       // field must not read as a range violation: ADVICE r04, it drove such a decoder through four re-calibrations to the fp32 chain)
-      constexpr bool kStrict = PL == 1 && ASDF16_P1_FOLD;
+      constexpr bool kStrict = PL == 1;
       if (kMix) { amax *= mul0; amax1 *= mul1; amax2 *= mul2; }      // (the maxima were taken in front of the rescale)
       const bool act_over = !(fmaxf(amax, fmaxf(amax1, amax2)) < 65504.0f);
       auto out_ok = [&](float v, float pre_v) { return kStrict ? fabsf(pre_v) < INFINITY : fabsf(v) <= 1.0f; };
@@ -1052,9 +921,7 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
         // with two point groups every lane folds ITS point: lanes 0..31 the first group's, lanes 32..63 the second's
         const long long pf_ = (G == 2 && half == 1) ? pib : pi;
         auto fold = [&](bool neg, int* rec, int extra) {
-#if ASDF16_FOLD_BALLOT
           if ((PL == 1 || kMix) && !__any(neg || extra != 0)) return;      // (wave-uniform: most tiles of a sweep hold no negative voxel; round 5: the split-half SeparateDecoder forms too)
-#endif
           int i0, i1, i2;                                        // (behind the early return: two integer divisions per lane)
           lattice_ijk(pf_, p.N, i0, i1, i2);
           int a0 = neg ? i0 : 0x7fffffff, a1 = neg ? i1 : 0x7fffffff, a2 = neg ? i2 : 0x7fffffff;
@@ -1079,12 +946,6 @@ __device__ __forceinline__ void sdf_mlp_f16_body(const DecodeParams& p) {
         const unsigned long long m = __ballot(bad);
         if (m && lane == 0) wrec[7] += __popcll(m);
       }
-      ASDF16_MARK(5);
-#ifdef ASDF16_SEGMENT_TIMES
-      if (blockIdx.x == 0 && wave == 0 && lane == 0 && slot == 0 && tile == (long long)blockIdx.x + 2 * gridDim.x)
-        { for (int k = 0; k < 6; ++k) g_seg[k] = (unsigned long long)seg_t[k]; g_seg[7] = (unsigned long long)seg_t[7]; }
-      if (blockIdx.x == 0 && wave == 0 && lane == 0 && slot == 0 && tile == (long long)blockIdx.x + 3 * gridDim.x) g_seg[6] = (unsigned long long)seg_t[0];
-#endif
     }   // tiles
 
     if (lane == 0) {

@@ -34,9 +34,7 @@
 
 namespace asdf {
 
-static_assert(ASDF16_STAGE_KB == 16 && ASDF16_MIX_SPLIT && ASDF16_EPI_STEPS && ASDF16_DMA_PER_KB && ASDF16_PRELOAD && ASDF16_LOADS_FIRST &&
-                  ASDF16_PIN_ACC,
-              "the W form is written for the shipped schedule of the split-half kernel");
+static_assert(ASDF16_STAGE_KB == 16, "the W form is written for the 32 KiB stages of the split-half kernel");
 
 #define ASDF_MFMA16W(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 #define ASDF_MFMA4W(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -117,7 +115,7 @@ __device__ __forceinline__ void stage16w(f32x16& acc, const h8 (&xh)[KB], const 
                                          Pre&& pre, Epi&& epi) {
   using SG = S16<2>;
   constexpr int PF = SG::kPrefetch;
-  constexpr int BKB = ASDF16_BARRIER_KB;
+  constexpr int BKB = kBarrierKb;
   constexpr int nslot = (SLOT + kRing - 1) % kRing;   // slot of stage (this - 1), refilled with stage (this + 3)
   static_assert(KB == 32 || KB == 16, "records per tile");
   static_assert(kS16Kb - BKB >= SG::kPieces, "one LDS-DMA piece per record behind the barrier");
@@ -299,7 +297,6 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
       f32x16 acc1[2], acc2[2], acc3[2];
       float pf2[2];                   // A fragments (fp32 MFMA) of the next layer-2 tile
       float w4c[2], w4n[2];           // last-layer weights of the current / next part of the layer-3 epilogue
-      constexpr int kPreKb = ASDF16_PRE_KB;
       static_assert(kPreKb >= kEpiShift + kEpiChunks, "preload K-block inside the epilogue slots");
       auto load_pf2 = [&](int t) { pf2[0] = pt_word(CL::kA2, t, 0); pf2[1] = pt_word(CL::kA2, t, 1); };
       auto load_w4 = [&](int t, int c) {        // accumulator registers 2 c, 2 c + 1 of tile t: group c >> 2, feature half (c >> 1) & 1,
