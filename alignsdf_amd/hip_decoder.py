@@ -8,6 +8,7 @@ libalignsdf_hip.so.
 """
 import collections
 import ctypes
+import logging
 import os
 
 import numpy as np
@@ -125,6 +126,19 @@ def kinematic_affine(point_feat_size, encode_style, scale_factor, mano_results, 
     return hand, np.concatenate([rows_hand[0]] + rows_obj_tail, 0)   # networks/model.py:297-299
 
 
+def decoder_layout(combined, point_feat_size, encode_style):
+    """(parameter prefixes, point features per head, outputs per MLP, the five (out, in) weight shapes per head) of the two decoder
+    kinds the kernels are built for: CombinedDecoder (one MLP, two outputs) and SeparateDecoder (a hand and an object MLP)."""
+    if combined:
+        prefixes, pf, n_out = ("lin",), (int(point_feat_size),), 2
+    else:
+        prefixes, pf, n_out = ("linh", "lino"), head_point_feats(int(point_feat_size), encode_style), 1
+    shapes = []
+    for n_in in (256 + f for f in pf):      # dims [512] * 4 behind a 256-wide latent, the skip concatenation in front of layer 2
+        shapes.append([(512, n_in), (512 - n_in, 512), (512, 512), (512, 512), (n_out, 512)])
+    return prefixes, pf, n_out, shapes
+
+
 def unsupported_reason(state_dict, latent_size, point_feat_size, encode_style):
     """Why (a string) the fused kernels cannot evaluate a decoder with these parameters, or None when they can.  The kernels are
     built for the shape every shipped AlignSDF config uses (experiments/*/*.json: LatentSize 256, dims [512] * 4, latent_in [2] -
@@ -136,24 +150,20 @@ def unsupported_reason(state_dict, latent_size, point_feat_size, encode_style):
     if any(k.startswith("bn") for k in keys):
         return "LayerNorm form (weight_norm false)"
     combined = "lin0.bias" in keys
-    prefixes = ("lin",) if combined else ("linh", "lino")
     if not combined and "linh0.bias" not in keys:
         return "not a SeparateDecoder / CombinedDecoder shaped module"
     if int(latent_size) != 256:
         return "LatentSize %d (the kernels fold a 256-wide latent)" % int(latent_size)
     if encode_style not in ("nerf", "hand", "obj", "both"):
         return "EncodeStyle %r" % (encode_style,)
-    pf = (int(point_feat_size),) if combined else head_point_feats(int(point_feat_size), encode_style)
+    prefixes, pf, _, shapes = decoder_layout(combined, point_feat_size, encode_style)
     if encode_style == "nerf" and int(point_feat_size) > 3 and int(point_feat_size) not in (9, 15):
         return "NeRF positional encoding with PointFeatSize %d (9 and 15 are built)" % int(point_feat_size)
-    n_out = 2 if combined else 1
-    for prefix, f in zip(prefixes, pf):
+    for prefix, f, want in zip(prefixes, pf, shapes):
         if not 1 <= f <= _native.MAX_POINT_FEATS or 512 - 256 - f < 1:
             return "%d point features per head" % f
         if (prefix + "5.bias") in keys or (prefix + "4.bias") not in keys:
             return "not five layers per MLP (dims other than [512, 512, 512, 512])"
-        n_in = 256 + f
-        want = [(512, n_in), (512 - n_in, 512), (512, 512), (512, 512), (n_out, 512)]
         for layer in range(5):
             name = "%s%d" % (prefix, layer)
             wkey = name + (".weight_v" if name + ".weight_v" in keys else ".weight")
@@ -214,27 +224,19 @@ class HipSdfDecoder:
             raise _native.NativeError(-4, "no gfx950 (MI355X) device visible - the HIP path has no CPU fallback")
         # NeRF positional encoding: PointFeatSize > 3 with EncodeStyle "nerf" (utils/mesh.py:49-55) - not affine in xyz
         self.nerf_features = self.point_feat_size > 3 and encode_style == "nerf"
-        if self.nerf_features and self.point_feat_size not in (9, 15):
-            raise NotImplementedError("NeRF positional encoding is supported for PointFeatSize 9 and 15")
         mode = _native.FEATURES_NERF if self.nerf_features else _native.FEATURES_AFFINE
-        if self.combined:
-            pf, prefixes, n_out = (self.point_feat_size,), ("lin",), 2
-            spec = _native.DecoderSpec(self.latent_size, 512, 1, (ctypes.c_int32 * 2)(pf[0], 0), (ctypes.c_int32 * 2)(2, 0), mode)
-        else:
-            pf, prefixes, n_out = head_point_feats(self.point_feat_size, encode_style), ("linh", "lino"), 1
-            spec = _native.DecoderSpec(self.latent_size, 512, 2, (ctypes.c_int32 * 2)(*pf), (ctypes.c_int32 * 2)(1, 1), mode)
+        prefixes, pf, n_out, shapes = decoder_layout(self.combined, self.point_feat_size, encode_style)
+        # (per head; the second entry of a CombinedDecoder stays 0)
+        spec = _native.DecoderSpec(self.latent_size, 512, len(pf), (ctypes.c_int32 * 2)(*pf), (ctypes.c_int32 * 2)(*[n_out] * len(pf)), mode)
         heads = (_native.HeadParams * 2)()
         keep = []
         for hi, prefix in enumerate(prefixes):
-            n_in = self.latent_size + pf[hi]
-            shapes = [(512, n_in), (512 - n_in, 512), (512, 512), (512, 512), (n_out, 512)]
-            for layer in range(5):
+            for layer, (rows, _) in enumerate(shapes[hi]):
                 name = "%s%d" % (prefix, layer)
                 w = _effective(sd, name)
                 b = sd[name + ".bias"].detach().float().cpu().contiguous()
-                if tuple(w.shape) != shapes[layer] or b.numel() != shapes[layer][0]:
-                    raise NotImplementedError("unsupported layer shape %s %s (expected %s)" % (
-                        name, tuple(w.shape), shapes[layer]))
+                if b.numel() != rows:                 # (the weights' shapes: unsupported_reason looked)
+                    raise NotImplementedError("unsupported layer shape %s: a bias of %d values for %d rows" % (name, b.numel(), rows))
                 keep += [w, b]
                 heads[hi].w[layer] = w.data_ptr()
                 heads[hi].b[layer] = b.data_ptr()
@@ -248,14 +250,13 @@ class HipSdfDecoder:
         if "classifier_head.weight" in sd:
             cw = sd["classifier_head.weight"].detach().float().cpu().contiguous()
             cb = sd["classifier_head.bias"].detach().float().cpu().contiguous()
-            if cw.dim() != 2 or cw.shape[1] != 512 or cb.numel() != cw.shape[0] or not 1 <= cw.shape[0] <= _native.MAX_CLASSES:
-                raise NotImplementedError("unsupported classifier_head shape %s" % (tuple(cw.shape),))
+            if cb.numel() != cw.shape[0]:
+                raise NotImplementedError("unsupported classifier_head shape %s: a bias of %d values" % (tuple(cw.shape), cb.numel()))
             with torch.cuda.device(self.device):
                 _native.check(L.asdf_decoder_set_classifier(handle, cw.data_ptr(), cb.data_ptr(), int(cw.shape[0])),
                               "asdf_decoder_set_classifier")
             self.num_class = int(cw.shape[0])
         self._pf = pf
-        self.pixel_align = False
         if pixel_align:
             why = pixel_align_refusal(self.combined, self.point_feat_size, self.encode_style, self.num_class)
             if why is not None:
@@ -271,6 +272,8 @@ class HipSdfDecoder:
     def _init_sweep_state(self):
         """Everything the sweep state machine keeps on the host (arithmetic in use, calibration of the activation scales, modes,
         allowance, counters): no device involved beyond set_math, so tests/test_sweep_state_machine.py can drive it on the CPU."""
+        self.pixel_align = False     # (__init__ switches it on behind set_math("f32"))
+        self._audit_restarts = 0     # whole-lattice comparisons so far: each restarts the audit's draw with another seed
         # arithmetic of the hidden GEMMs: "f32" (fp32 MFMA chain) or "f16x3" (split-half fp16 MFMA, fp32-class results);
         # ASDF_MATH overrides the default
         self.math = "f32"
@@ -356,14 +359,14 @@ class HipSdfDecoder:
         """Opt in to (or out of) the audited one-plane sweeps for mesh-producing calls: coarse "box" + fine "band" (what ASDF_FAST=1 /
         `--fast` select when the decoder is packed), or ordinary sweeps in both passes - the default.  A pixel-aligned decoder has
         ordinary sweeps only: set_fast(True) raises."""
-        if on and getattr(self, "pixel_align", False):
+        if on and self.pixel_align:
             raise ValueError("a pixel-aligned decoder runs ordinary fp32 sweeps only: the one-plane sweeps (--fast) do not cover it")
         self.coarse_mode, self.fine_mode = (FAST_COARSE, FAST_FINE) if on else ("exact", "exact")
 
     def set_math(self, math):
         """Select the arithmetic of the hidden GEMMs ("f32" / "f16x3"); raises for NeRF-encoded decoders and f16x3."""
         code = {"f32": _native.MATH_F32, "f16x3": _native.MATH_F16X3}[math]
-        if math != "f32" and getattr(self, "pixel_align", False):
+        if math != "f32" and self.pixel_align:
             raise ValueError("a pixel-aligned decoder runs the fp32 MFMA chain only (math='f32'), not %r" % math)
         _native.check(self._L.asdf_decoder_set_math(self._h, code), "asdf_decoder_set_math")
         self.math = math
@@ -388,7 +391,6 @@ class HipSdfDecoder:
         fault = _native.REC_STATUS + _native.STATUS_CLUSTER_FAULT
         hit = bool(int(rec[_native.BOX_RANGE]) & CLUSTER_FAULT_BIT) or (len(rec) > fault and int(rec[fault]) != 0)
         if hit and not self._cluster_off:
-            import logging
             logging.warning("short-list kernel: a member of a cluster did not arrive in time; the tile form evaluated the list, the cluster "
                             "form is switched off for this decoder")
             self._cluster_off = True
@@ -410,7 +412,6 @@ class HipSdfDecoder:
         bad, near_over = self._range_words(bbox_host)
         self._note_cluster_fault(bbox_host)
         if near_over:
-            import logging
             logging.warning("split-half sweep: more than %d voxels within %.1e of the level; repeated on the fp32 chain", NEAR_CAP, self.refine_tau)
             self._force_f32_once = True
         if not bad:
@@ -428,7 +429,6 @@ class HipSdfDecoder:
 
     def _to_f32(self, bad):
         if self.math != "f32":
-            import logging
             logging.warning("split-half decoder: %d activations left the fp16 range; falling back to the fp32 MFMA kernel", bad)
             self.set_math("f32")
             self.events["fp32_fallback"] = True
@@ -484,7 +484,6 @@ class HipSdfDecoder:
                     new[h, l] = float(np.clip(want, 2.0 ** -24, 2.0 ** 24))
         if np.array_equal(new, cur):
             return False
-        import logging
         logging.info("split-half decoder: activation scales %s -> %s", cur.tolist(), new.tolist())
         self.set_act_scales(new)
         return True
@@ -541,7 +540,7 @@ class HipSdfDecoder:
         1 KB is a shader blit that cannot get a wave slot while a persistent sweep owns every compute unit (round 5's eval-mode
         trace: 21.5 ms per sample resident), and a plain `.to(device)` of pageable memory makes the caller wait
         for everything queued."""
-        if getattr(self, "pixel_align", False):
+        if self.pixel_align:
             raise ValueError("a pixel-aligned decoder binds its samples with set_sample_pixel (feature map, cam_intr, root joint)")
         if latent_vec.numel() != self.latent_size:
             raise ValueError("latent has %d elements, expected %d" % (latent_vec.numel(), self.latent_size))
@@ -587,7 +586,7 @@ class HipSdfDecoder:
         `cam_intr` [1, 3, 4] (or [3, 4]), the root joint `root_joint` (mano_results["joints"][:, 0], camera space, 3 values),
         specs["ImageSize"][0] and specs["SdfScaleFactor"] (asdf_decoder_set_sample_pixel).  The map stays referenced until the next
         bind: the projection kernels read it in stream order."""
-        if not getattr(self, "pixel_align", False):
+        if not self.pixel_align:
             raise ValueError("set_sample_pixel needs a decoder built with pixel_align=True")
         f = torch.as_tensor(feat).detach()
         if f.dim() != 4 or f.shape[0] != 1:
@@ -605,6 +604,27 @@ class HipSdfDecoder:
                                                                  (ctypes.c_float * 3)(*root.tolist()), ctypes.c_float(float(image_size)),
                                                                  ctypes.c_float(float(scale_factor)), self._stream()),
                           "asdf_decoder_set_sample_pixel")
+
+    def _sweep_args(self, N, origin3, voxel_size, lattice, grid_mode, tau, hand, obj, record):
+        """Positional arguments of a sweep's entry point in the C ABI's order: h, N, (lattice | origin[3], voxel), grid_mode, [tau],
+        hand, obj, record, stream.  `lattice` (device float32[4]): the _dev forms; `tau`: the one-plane entry points (None for an
+        ordinary sweep); `hand`, `obj`, `record`: the output tensors, None for one that is not wanted."""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        if lattice is not None:
+            where = [lattice.data_ptr()]
+        else:
+            where = [(ctypes.c_float * 3)(*[float(np.float32(o)) for o in origin3]), ctypes.c_float(float(np.float32(voxel_size)))]
+        allowance = [ctypes.c_float(float(tau))] if tau is not None else []
+        return [self._h, int(N)] + where + [int(grid_mode)] + allowance + [ptr(hand), ptr(obj), ptr(record), self._stream()]
+
+    def _time_next_sweep(self):
+        """A pair of timing events that the library records around the decoder kernel of the NEXT sweep itself, not around the bbox /
+        refinement kernels next to it; a first record() makes torch create the handles."""
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        for e in ev:
+            e.record()
+        _native.check(self._L.asdf_decoder_time_next_sweep(self._h, *[ctypes.c_void_p(e.cuda_event) for e in ev]), "asdf_decoder_time_next_sweep")
+        return ev
 
     def decode_grid(self, N, origin3, voxel_size, grid_mode=_native.GRID_REFERENCE, want_bbox=True, hand=True, obj=True,
                     check_range=None, lattice=None):
@@ -624,7 +644,7 @@ class HipSdfDecoder:
         hand = torch.empty((N, N, N), dtype=torch.float32, device=self.device) if hand else None
         obj = torch.empty((N, N, N), dtype=torch.float32, device=self.device) if obj else None
         bbox = torch.empty(16, dtype=torch.int32, device=self.device) if want_bbox else None
-        org = (ctypes.c_float * 3)(*[float(np.float32(o)) for o in origin3]) if lattice is None else None
+        name = "asdf_decode_grid" if lattice is None else "asdf_decode_grid_dev"
         guard = self.math == "f16x3" and not want_bbox and (check_range is None or check_range)
         once_f32 = self._force_f32_once and self.math == "f16x3"
         self._force_f32_once = False
@@ -633,28 +653,9 @@ class HipSdfDecoder:
             guard = False
 
         def launch():
-            ev = None
             with torch.cuda.device(self.device):
-                if self.event_log is not None:
-                    # the events bracket the decoder kernel itself (asdf_decoder_time_next_sweep), not the bbox / refinement
-                    # kernels around it; a first record() makes torch create the handles
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
-                    ev[1].record()
-                    _native.check(self._L.asdf_decoder_time_next_sweep(self._h, ctypes.c_void_p(ev[0].cuda_event),
-                                                                       ctypes.c_void_p(ev[1].cuda_event)), "asdf_decoder_time_next_sweep")
-                if lattice is not None:
-                    _native.check(self._L.asdf_decode_grid_dev(self._h, int(N), lattice.data_ptr(), int(grid_mode),
-                                                               hand.data_ptr() if hand is not None else None,
-                                                               obj.data_ptr() if obj is not None else None,
-                                                               bbox.data_ptr() if want_bbox else None, self._stream()),
-                                  "asdf_decode_grid_dev")
-                else:
-                    _native.check(self._L.asdf_decode_grid(self._h, int(N), org, ctypes.c_float(float(np.float32(voxel_size))),
-                                                           int(grid_mode), hand.data_ptr() if hand is not None else None,
-                                                           obj.data_ptr() if obj is not None else None,
-                                                           bbox.data_ptr() if want_bbox else None, self._stream()),
-                                  "asdf_decode_grid")
+                ev = self._time_next_sweep() if self.event_log is not None else None
+                _native.check(getattr(self._L, name)(*self._sweep_args(N, origin3, voxel_size, lattice, grid_mode, None, hand, obj, bbox)), name)
             return ev
 
         # A split-half sweep that evaluates an MLP whose activation scales are still at their default calibrates them from
@@ -700,24 +701,11 @@ class HipSdfDecoder:
         sh = torch.empty((N, N, N), dtype=torch.float32, device=self.device) if hand else None
         so = torch.empty((N, N, N), dtype=torch.float32, device=self.device) if obj else None
         rec = torch.empty(REC_WORDS, dtype=torch.int32, device=self.device)
-        org = (ctypes.c_float * 3)(*[float(np.float32(o)) for o in origin3]) if lattice is None else None
         with torch.cuda.device(self.device):
-            ev = None
             self._box_event_tick += 1
-            if self.box_event_log is not None and self._box_event_tick % self.box_event_stride == 0:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
-                ev[1].record()
-                _native.check(self._L.asdf_decoder_time_next_sweep(self._h, ctypes.c_void_p(ev[0].cuda_event),
-                                                                   ctypes.c_void_p(ev[1].cuda_event)), "asdf_decoder_time_next_sweep")
-            if lattice is not None:
-                _native.check(fn(self._h, int(N), lattice.data_ptr(), int(grid_mode), ctypes.c_float(float(tau)),
-                                 sh.data_ptr() if sh is not None else None, so.data_ptr() if so is not None else None, rec.data_ptr(),
-                                 self._stream()), name)
-            else:
-                _native.check(fn(self._h, int(N), org, ctypes.c_float(float(np.float32(voxel_size))), int(grid_mode),
-                                 ctypes.c_float(float(tau)), sh.data_ptr() if sh is not None else None,
-                                 so.data_ptr() if so is not None else None, rec.data_ptr(), self._stream()), name)
+            timed = self.box_event_log is not None and self._box_event_tick % self.box_event_stride == 0
+            ev = self._time_next_sweep() if timed else None
+            _native.check(fn(*self._sweep_args(N, origin3, voxel_size, lattice, grid_mode, tau, sh, so, rec)), name)
             if ev is not None:
                 self.box_event_log.append(ev + (rec,))      # (words 28..31 of the record: shader-clock stamps of the sweep kernel)
         return rec, sh, so
@@ -827,6 +815,15 @@ class HipSdfDecoder:
         ev.record(torch.cuda.current_stream(self.device))
         return slot, n, ev
 
+    def _ticket(self, kind, args, rec, host=True, **optional):
+        """The ticket of the sweep just enqueued, a plain dict: kind ("box" | "band" | "exact"), the arguments to repeat it with, its
+        device record, the scale epoch and - unless `host` is False - the record's pinned copy, enqueued here.  `optional`: `keep`
+        (volumes to keep alive), `tau`, `recalibrate`."""
+        ticket = dict(optional, **{"kind": kind, "args": args, "rec": rec, "epoch": self._recalibrations})
+        if host:
+            ticket["host"] = self._record_to_host(rec)
+        return ticket
+
     @staticmethod
     def _record_of(ticket):
         """The ticket's record as a host array (waits for the sweep it belongs to, and for nothing queued behind it)."""
@@ -871,18 +868,15 @@ class HipSdfDecoder:
                                                         self._coarse_since_cal > 2 * RECAL_EVERY)      # (no fine pass took its turn)
         if self._box_usable() and self._allowance_valid(N) and not self._force_f32_once and not due:
             rec, sh, so = self._box_launch(*args, self._box_tau)
-            return {"kind": "box", "args": args, "rec": rec, "keep": (sh, so), "tau": self._box_tau, "epoch": self._recalibrations,
-                    "host": self._record_to_host(rec)}
+            return self._ticket("box", args, rec, keep=(sh, so), tau=self._box_tau)
         h, o, bbox = self.decode_grid(N, origin3, voxel_size, grid_mode, hand=hand, obj=obj)
-        return {"kind": "exact", "args": args, "rec": bbox, "keep": (h, o), "epoch": self._recalibrations, "recalibrate": due,
-                "host": self._record_to_host(bbox)}
+        return self._ticket("exact", args, bbox, keep=(h, o), recalibrate=due)
 
     def coarse_judge(self, ticket):
         """Verdict on a box-only coarse sweep WITHOUT launching anything: (accepted, int32[16] record or None, calibrate_allowance).
         Waits for the sweep's record (and for nothing queued behind it).  A refusal is booked here - counters, failure streak, new
         activation scales after a range violation - so that the caller only has to repeat the pass as an ordinary sweep
         (coarse_finish(ticket, judged=...)) while the decoder is bound to the ticket's sample."""
-        import logging
         N = ticket["args"][0]
         r = self._record_of(ticket)
         if ticket["kind"] == "exact":
@@ -936,7 +930,7 @@ class HipSdfDecoder:
             if ok:
                 return b
             h, o, bbox = self.decode_grid(N, origin3, voxel_size, grid_mode, hand=hand, obj=obj)
-            ticket = {"kind": "exact", "args": ticket["args"], "rec": bbox, "keep": (h, o), "epoch": self._recalibrations}
+            ticket = self._ticket("exact", ticket["args"], bbox, host=False, keep=(h, o))      # (read with .cpu() right below)
         b = self._record_of(ticket)
         keep, epoch = ticket["keep"], ticket["epoch"]
         while self.fall_back_if_overflowed(b, epoch):      # split-half planes out of fp16 range: re-calibrated, or at last fp32
@@ -981,45 +975,41 @@ class HipSdfDecoder:
         step by step (can_speculate / can_speculate_ordinary), else a ticket: `coarse` / `fine` (tickets for coarse_judge /
         fine_needs_repeat), `lattice` (device float32[4]: origin, voxel size), `lattice_host` (pinned copy + event), `vol_hand` /
         `vol_obj` (the fine volumes)."""
-        if not self.can_speculate(N):
-            if not self.can_speculate_ordinary(hand, obj):
-                return None
-            # ---- ordinary sweeps in both passes, enqueued in one go
-            self.events["samples_in_one_go"] += 1
-            org = [-1.0, -1.0, -1.0]
-            args = (N, org, voxel_size, grid_mode, hand, obj)
-            h, o, bbox = self.decode_grid(N, org, voxel_size, grid_mode, hand=hand, obj=obj)
-            coarse = {"kind": "exact", "args": args, "rec": bbox, "keep": (h, o), "epoch": self._recalibrations, "host": self._record_to_host(bbox)}
-            lattice = torch.empty(4, dtype=torch.float32, device=self.device)
-            with torch.cuda.device(self.device):
-                _native.check(self._L.asdf_zoom_cube(bbox.data_ptr(), int(N), ctypes.c_float(float(np.float32(voxel_size))), int(bool(hand)),
-                                                     int(bool(obj)), lattice.data_ptr(), self._stream()), "asdf_zoom_cube")
-            lattice_host = self._record_to_host(lattice.view(torch.int32))
-            vh, vo, bbox2 = self.decode_grid(N, None, None, grid_mode, want_bbox=self.math == "f16x3", hand=hand, obj=obj, lattice=lattice)
-            fine = {"kind": "exact", "args": (N, None, None, grid_mode, hand, obj), "rec": bbox2, "epoch": self._recalibrations,
-                    "host": self._record_to_host(bbox2)}
-            return {"coarse": coarse, "fine": fine, "lattice": lattice, "lattice_host": lattice_host, "vol_hand": vh, "vol_obj": vo}
+        one_plane = self.can_speculate(N)
+        if not one_plane and not self.can_speculate_ordinary(hand, obj):
+            return None
         # (a CombinedDecoder evaluates both columns whatever the flags say - the launches force that themselves - but the ZOOM CUBE and
         # the marching-cubes parts follow the caller's HandBranch / ObjectBranch like get_higher_res_cube, utils/mesh.py:239-247, and the
         # step-by-step path: ADVICE r05)
-        self._coarse_since_cal += 1
         self.events["samples_in_one_go"] += 1
-        tau = self._box_tau
         org = [-1.0, -1.0, -1.0]
-        args = (N, org, voxel_size, grid_mode, hand, obj)
-        rec, sh, so = self._box_launch(*args, tau)
-        coarse = {"kind": "box", "args": args, "rec": rec, "keep": (sh, so), "tau": tau, "epoch": self._recalibrations,
-                  "host": self._record_to_host(rec)}
+        args, fine_args = (N, org, voxel_size, grid_mode, hand, obj), (N, None, None, grid_mode, hand, obj)
+        if one_plane:
+            self._coarse_since_cal += 1
+            tau = self._box_tau
+            rec, sh, so = self._box_launch(*args, tau)
+            coarse = self._ticket("box", args, rec, keep=(sh, so), tau=tau)
+        else:
+            h, o, rec = self.decode_grid(N, org, voxel_size, grid_mode, hand=hand, obj=obj)
+            coarse = self._ticket("exact", args, rec, keep=(h, o))
+        lattice, lattice_host = self._zoom_cube(rec, N, voxel_size, hand, obj)
+        if one_plane:
+            rec2, vh, vo = self._one_plane_launch(self._L.asdf_decode_grid_band_dev, "asdf_decode_grid_band_dev", N, None, None, grid_mode,
+                                                  hand, obj, tau, lattice=lattice)
+            fine = self._ticket("band", fine_args, rec2, tau=tau)
+        else:
+            vh, vo, rec2 = self.decode_grid(N, None, None, grid_mode, want_bbox=self.math == "f16x3", hand=hand, obj=obj, lattice=lattice)
+            fine = self._ticket("exact", fine_args, rec2)
+        return {"coarse": coarse, "fine": fine, "lattice": lattice, "lattice_host": lattice_host, "vol_hand": vh, "vol_obj": vo}
+
+    def _zoom_cube(self, record, N, voxel_size, hand, obj):
+        """Enqueue the zoom cube of a coarse sweep's device `record` and, right behind it - IN FRONT of the fine sweep: its reader must
+        not wait for that - the lattice's copy to the host.  Returns (device float32[4]: origin, voxel size; pinned copy + event)."""
         lattice = torch.empty(4, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _native.check(self._L.asdf_zoom_cube(rec.data_ptr(), int(N), ctypes.c_float(float(np.float32(voxel_size))), int(bool(hand)),
+            _native.check(self._L.asdf_zoom_cube(record.data_ptr(), int(N), ctypes.c_float(float(np.float32(voxel_size))), int(bool(hand)),
                                                  int(bool(obj)), lattice.data_ptr(), self._stream()), "asdf_zoom_cube")
-        lattice_host = self._record_to_host(lattice.view(torch.int32))      # (behind the zoom kernel, IN FRONT of the fine sweep: its reader must not wait for that)
-        rec2, vh, vo = self._one_plane_launch(self._L.asdf_decode_grid_band_dev, "asdf_decode_grid_band_dev", N, None, None, grid_mode,
-                                              hand, obj, tau, lattice=lattice)
-        fine = {"kind": "band", "args": (N, None, None, grid_mode, hand, obj), "rec": rec2, "tau": tau, "epoch": self._recalibrations,
-                "host": self._record_to_host(rec2)}
-        return {"coarse": coarse, "fine": fine, "lattice": lattice, "lattice_host": lattice_host, "vol_hand": vh, "vol_obj": vo}
+        return lattice, self._record_to_host(lattice.view(torch.int32))
 
     @classmethod
     def lattice_of(cls, ticket):
@@ -1044,11 +1034,10 @@ class HipSdfDecoder:
         if band and not self._band_skip and self._allowance_valid(N) and self._fine_valid(N) and not fine_due:
             rec, vh, vo = self._one_plane_launch(self._L.asdf_decode_grid_band, "asdf_decode_grid_band", N, origin3, voxel_size,
                                                  grid_mode, hand, obj, self._box_tau)
-            return vh, vo, {"kind": "band", "args": args, "rec": rec, "tau": self._box_tau, "epoch": self._recalibrations,
-                            "host": self._record_to_host(rec)}
+            return vh, vo, self._ticket("band", args, rec, tau=self._box_tau)
         self._band_skip = False
         vh, vo, bbox2 = self.decode_grid(N, origin3, voxel_size, grid_mode, want_bbox=self.math == "f16x3", hand=hand, obj=obj)
-        ticket = {"kind": "exact", "args": args, "rec": bbox2, "epoch": self._recalibrations, "host": self._record_to_host(bbox2)}
+        ticket = self._ticket("exact", args, bbox2)
         if band and self.math == "f16x3" and (fine_due or not self._fine_valid(N)) and not self._fine_compare_in_flight:
             # the zoom lattice is compared as a whole: this ordinary sweep (whose volumes the caller gets) against a plain one-plane
             # sweep of the same lattice, enqueued here while the decoder is bound to the sample and evaluated in fine_needs_repeat
@@ -1065,7 +1054,6 @@ class HipSdfDecoder:
         if ticket is None:
             return False
         if ticket["kind"] == "band":
-            import logging
             r = self._record_of(ticket)
             if ticket["epoch"] != self._recalibrations:
                 # not judged: its error says nothing about the current scales.  (A near-level list that overflowed is a property of
@@ -1111,7 +1099,7 @@ class HipSdfDecoder:
         audit = self.audit_voxels
         self.set_audit(0)
         out = self._box_launch(*args, 1e-7)
-        self._audit_restarts = getattr(self, "_audit_restarts", 0) + 1
+        self._audit_restarts += 1
         self.set_audit(audit, seed=0x5DF5A11D00000000 + 0x9E3779B9 * self._audit_restarts)
         return out
 
@@ -1125,7 +1113,7 @@ class HipSdfDecoder:
         ladder = self.LADDER
         sample_max = np.zeros(len(ladder))
         gen = torch.Generator(device=self.device)
-        gen.manual_seed(12345 + getattr(self, "_audit_restarts", 0))
+        gen.manual_seed(12345 + self._audit_restarts)
         for fast, exact in zip(fast_vols, exact_vols):
             if fast is not None and exact is not None:
                 signed = (fast - exact).reshape(-1)
@@ -1148,7 +1136,6 @@ class HipSdfDecoder:
     def _apply_comparison(self, m, N, which):
         """Take a whole-lattice comparison (_compare_lattices) into the allowance, the tail ladder and the certificate.  `which` =
         "coarse" | "fine".  Returns False when it switched one-plane sweeps off."""
-        import logging
         err, sigma, corr = m["err"], m["sigma"], m["corr"]
         c = self.cert
         fresh = c["calibrations"] + c["fine_calibrations"] == 0 or not self._err_window
@@ -1257,7 +1244,7 @@ class HipSdfDecoder:
         d = lambda now, then, k: int(now[k]) - int(then[k])
         c = self.cert
         extra = {}
-        if getattr(self, "pixel_align", False):
+        if self.pixel_align:
             extra["pixel_align"] = {"path": "native (fp32 MFMA chain, pixel-aligned form)", "fast_sweeps": "not applied: a pixel-aligned "
                                     "decoder runs ordinary fp32 sweeps only", "ignored_settings": dict(self._fast_not_applied)}
         return dict(extra, **{

@@ -101,6 +101,33 @@ def test_lattice_from_device_memory_gives_the_same_volumes(tag):
     hip.close()
 
 
+@pytest.mark.parametrize("N", [5, 6])
+def test_the_host_launchers_hand_both_lattice_forms_the_same_lattice(N):
+    """HipSdfDecoder.decode_grid and _one_plane_launch build the argument list of the by-value and of the device-lattice entry points
+    (the test above calls the library itself): the same four floats either way give bit-equal volumes and equal records, in both index
+    modes, on 125 points (less than one 128-point workgroup tile) and 216 (a full tile and a partial one)."""
+    from tests.test_gpu_coarse_box import _bind, _decoder
+    hip, specs = _decoder("nerf3")
+    origin, voxel = [-0.62, -0.36, -0.37], float(np.float32(1.21 / (N - 1)))
+    lat = torch.tensor(origin + [voxel], dtype=torch.float32, device="cuda")
+    _bind(hip, specs, 1)
+    hip.decode_grid(64, [-1.0, -1.0, -1.0], 2.0 / 63)               # calibrates the activation scales
+    _bind(hip, specs, 1)
+    hip.set_audit(0)                                                # (its picks are a random stream that advances per call)
+    L = hip._L
+    for mode in (_native.GRID_REFERENCE, _native.GRID_INTEGER):
+        a_h, a_o, a_b = hip.decode_grid(N, origin, voxel, mode)
+        b_h, b_o, b_b = hip.decode_grid(N, None, None, mode, lattice=lat)
+        assert torch.equal(a_h, b_h) and torch.equal(a_o, b_o) and torch.equal(a_b, b_b), mode
+        a_r, a_h, a_o = hip._one_plane_launch(L.asdf_decode_grid_band, "asdf_decode_grid_band", N, origin, voxel, mode, True, True, 2e-3)
+        b_r, b_h, b_o = hip._one_plane_launch(L.asdf_decode_grid_band_dev, "asdf_decode_grid_band_dev", N, None, None, mode, True, True, 2e-3,
+                                              lattice=lat)
+        a_r, b_r = a_r.cpu().numpy().copy(), b_r.cpu().numpy().copy()
+        a_r[28:32] = b_r[28:32] = 0                                 # (shader-clock stamps of the sweep kernel)
+        assert torch.equal(a_h, b_h) and torch.equal(a_o, b_o) and np.array_equal(a_r, b_r), mode
+    hip.close()
+
+
 @pytest.mark.parametrize("tag,N", [("nerf3", 64), ("both9", 96), ("grasp3", 128), ("nerf9", 64)])
 def test_samples_enqueued_in_one_go_give_the_step_by_step_meshes(tag, N, monkeypatch):
     """The sample pipeline with and without the speculation: zoom cubes bit-equal, vertices and faces torch.equal, for 12 samples; the

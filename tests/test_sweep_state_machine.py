@@ -58,10 +58,11 @@ REASONS = {"range": (_range, False), "near": (_near, False), "near_bit": (_near_
 
 
 class FakeLib:
-    """Logs (entry point, arithmetic in force) and writes the next scripted record into the caller's buffer."""
+    """Logs (entry point, arithmetic in force) and, in `calls`, (entry point, positional arguments as received); writes the next
+    scripted record into the caller's buffer."""
 
     def __init__(self, dec):
-        self.dec, self.log, self.script = dec, [], []
+        self.dec, self.log, self.script, self.calls = dec, [], [], []
 
     def _write(self, ptr, words):
         buf = (ctypes.c_int32 * len(words)).from_address(ptr)
@@ -69,33 +70,41 @@ class FakeLib:
 
     def asdf_decode_grid(self, h, n, org, vs, mode, hand, obj, bbox, stream):
         self.log.append(("grid", self.dec.math))
+        self.calls.append(("asdf_decode_grid", (h, n, org, vs, mode, hand, obj, bbox, stream)))
         if bbox:
             self._write(bbox, good_record(1.0)[:16])
         return 0
 
     def asdf_decode_grid_dev(self, h, n, lattice, mode, hand, obj, bbox, stream):
         self.log.append(("grid_dev", self.dec.math))
+        self.calls.append(("asdf_decode_grid_dev", (h, n, lattice, mode, hand, obj, bbox, stream)))
         if bbox:
             self._write(bbox, self.grid_dev_record if getattr(self, "grid_dev_record", None) is not None else good_record(1.0)[:16])
         return 0
 
-    def _one_plane(self, name, rec):
+    def _one_plane(self, name, rec, args):
         self.log.append((name, self.dec.math))
+        self.calls.append(("asdf_decode_grid_" + name, args))
         self._write(rec, self.script.pop(0))
         return 0
 
     def asdf_decode_grid_box(self, h, n, org, vs, mode, tau, sh, so, rec, stream):
-        return self._one_plane("box", rec)
+        return self._one_plane("box", rec, (h, n, org, vs, mode, tau, sh, so, rec, stream))
 
     def asdf_decode_grid_band(self, h, n, org, vs, mode, tau, sh, so, rec, stream):
-        return self._one_plane("band", rec)
+        return self._one_plane("band", rec, (h, n, org, vs, mode, tau, sh, so, rec, stream))
 
     def asdf_decode_grid_band_dev(self, h, n, lattice, mode, tau, sh, so, rec, stream):
-        return self._one_plane("band_dev", rec)
+        return self._one_plane("band_dev", rec, (h, n, lattice, mode, tau, sh, so, rec, stream))
 
     def asdf_zoom_cube(self, bbox, n, vs, hand, obj, lattice, stream):
         self.log.append(("zoom", self.dec.math))
+        self.calls.append(("asdf_zoom_cube", (bbox, n, vs, hand, obj, lattice, stream)))
         (ctypes.c_float * 4).from_address(lattice)[:] = [-0.5, -0.25, -0.125, 0.0078125]
+        return 0
+
+    def asdf_decoder_time_next_sweep(self, h, ev0, ev1):
+        self.log.append(("time_next_sweep", (ev0.value, ev1.value)))
         return 0
 
     def asdf_decoder_set_math(self, h, code):
@@ -640,3 +649,187 @@ def test_a_range_violation_in_a_speculative_ordinary_coarse_pass_is_recovered_on
     assert [k for k, _ in dec._L.log] == ["grid"] and recovered == [12] and b[7] == 0 and dec.box_stats["exact"] == 1
     # the fine pass of that sample was launched under the old scales: its record is judged as stale and it is repeated
     assert dec.fine_needs_repeat(dict(t["fine"], rec=torch.from_numpy(bad.copy()), host=None)) is True
+
+
+# ---- the launch side as a table: what the native entry points receive, which tickets come back ------------------------------------
+ORG, VS, TAU = [-0.62, -0.36, -0.37], 1.21 / 63, 0.0123             # (none of them an fp32 number: the roundings show)
+R32 = lambda x: float(np.float32(x))
+# entry point, lattice by value (origin[3], voxel) or as a device pointer, takes an allowance
+LAUNCHES = [("asdf_decode_grid", True, False), ("asdf_decode_grid_dev", False, False), ("asdf_decode_grid_box", True, True),
+            ("asdf_decode_grid_band", True, True), ("asdf_decode_grid_band_dev", False, True)]
+
+
+def _plain(a):
+    """An argument as FakeLib received it, comparable: ctypes floats by type and value."""
+    if isinstance(a, ctypes.c_float):
+        return ("c_float", a.value)
+    if isinstance(a, ctypes.Array):
+        assert a._type_ is ctypes.c_float
+        return ("c_float[%d]" % len(a), list(a))
+    return a
+
+
+def _launch(dec, entry, by_value, mode, hand, obj, lat):
+    """One launch of `entry` through the method the product uses for it; returns (record, sdf_hand, sdf_obj)."""
+    if entry == "asdf_decode_grid":
+        h, o, rec = dec.decode_grid(5, ORG, VS, mode, hand=hand, obj=obj)
+    elif entry == "asdf_decode_grid_dev":
+        h, o, rec = dec.decode_grid(5, None, None, mode, hand=hand, obj=obj, lattice=lat)
+    elif entry == "asdf_decode_grid_box":
+        rec, h, o = dec._box_launch(5, ORG, VS, mode, hand, obj, TAU)
+    else:
+        rec, h, o = dec._one_plane_launch(getattr(dec._L, entry), entry, 5, ORG if by_value else None, VS if by_value else None, mode,
+                                          hand, obj, TAU, lattice=None if by_value else lat)
+    return rec, h, o
+
+
+@pytest.mark.parametrize("hand,obj", [(True, True), (True, False), (False, True)])
+@pytest.mark.parametrize("entry,by_value,has_tau", LAUNCHES)
+def test_what_every_sweep_entry_point_receives(machine, entry, by_value, has_tau, hand, obj):
+    """The C ABI, argument by argument: h, N, (lattice | origin[3], voxel), grid_mode, [tau], hand, obj, record, stream - origin and
+    voxel size rounded to fp32, tau a c_float, None for a head that is switched off, the lattice's pointer in the _dev forms."""
+    dec, _ = machine
+    H, S = object(), object()
+    dec._h, dec._stream = H, lambda: S
+    lat = torch.tensor(ORG + [VS], dtype=torch.float32)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    for mode in (0, 1):
+        dec._L.script = [good_record(1.0)]
+        dec._L.calls.clear()
+        rec, h, o = _launch(dec, entry, by_value, mode, hand, obj, lat)
+        assert (h is not None, o is not None) == (hand, obj) and all(v.shape == (5, 5, 5) and v.dtype == torch.float32 for v in (h, o) if v is not None)
+        assert rec.dtype == torch.int32 and rec.numel() == (hd.REC_WORDS if has_tau else 16)
+        want = [H, 5] + ([("c_float[3]", [R32(v) for v in ORG]), ("c_float", R32(VS))] if by_value else [lat.data_ptr()]) + [mode]
+        want += ([("c_float", R32(TAU))] if has_tau else []) + [ptr(h), ptr(o), rec.data_ptr(), S]
+        (name, got), = dec._L.calls
+        assert name == entry and [_plain(a) for a in got] == want
+    if not has_tau:
+        # an ordinary sweep without a box record: None in its place
+        dec._L.calls.clear()
+        assert _launch_no_bbox(dec, by_value, lat) is None and dec._L.calls[-1][1][-2] is None
+    # a CombinedDecoder evaluates both columns whatever the flags say
+    dec.combined = True
+    dec._L.script = [good_record(1.0)]
+    dec._L.calls.clear()
+    rec, h, o = _launch(dec, entry, by_value, 0, hand, obj, lat)
+    assert dec._L.calls[0][1][-4:-2] == (h.data_ptr(), o.data_ptr())
+    dec._h = None
+
+
+def _launch_no_bbox(dec, by_value, lat):
+    return dec.decode_grid(5, ORG if by_value else None, VS if by_value else None, 0, want_bbox=False, lattice=None if by_value else lat)[2]
+
+
+class FakeEvent:
+    """Stand-in for torch.cuda.Event: counts its record() calls."""
+    made = 0
+
+    def __init__(self, enable_timing=False):
+        FakeEvent.made += 1
+        self.cuda_event, self.timing, self.records = 1000 + FakeEvent.made, enable_timing, 0
+
+    def record(self, stream=None):
+        self.records += 1
+
+
+def test_which_launches_are_bracketed_by_events(machine, monkeypatch):
+    """asdf_decoder_time_next_sweep takes a fresh pair of timing events, each recorded once, right in front of the launch.  decode_grid
+    logs only the pair of the launch whose volumes it returns; the one-plane path counts every launch and logs (ev0, ev1, record) of
+    every box_event_stride-th."""
+    dec, calls = machine
+    monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
+    timed = lambda: [v for k, v in dec._L.log if k == "time_next_sweep"]
+    kinds = lambda: [k for k, _ in dec._L.log]
+    # an ordinary sweep without a box record whose first launch reports a range violation: launched twice, the second pair is logged
+    answers = [np.zeros(16, dtype=np.int32), np.zeros(16, dtype=np.int32), np.zeros(16, dtype=np.int32)]
+    answers[1][hd._native.STATUS_RANGE] = 3
+    dec._status = lambda clear: answers.pop(0)
+    dec.event_log = []
+    dec.decode_grid(5, ORG, VS, want_bbox=False)
+    assert kinds() == ["time_next_sweep", "grid", "time_next_sweep", "grid"] and calls == ["recover"]
+    (ev0, ev1), = dec.event_log
+    assert (ev0.cuda_event, ev1.cuda_event) == timed()[1] != timed()[0] and ev0.timing and ev1.timing and (ev0.records, ev1.records) == (1, 1)
+    dec.event_log = None
+    dec._L.log.clear()
+    dec.decode_grid(5, ORG, VS)
+    assert kinds() == ["grid"]
+    # one-plane sweeps: no log, no events, but every launch counts
+    dec._L.script = [good_record(1.0) for _ in range(6)]
+    dec._L.log.clear()
+    made = FakeEvent.made
+    dec._box_launch(5, ORG, VS, 0, True, True, TAU)
+    assert dec._box_event_tick == 1 and kinds() == ["box"] and FakeEvent.made == made
+    dec.box_event_log, dec.box_event_stride = [], 2
+    recs = [dec._box_launch(5, ORG, VS, 0, True, True, TAU)[0] for _ in range(5)]          # launches 2 .. 6: 2, 4 and 6 are bracketed
+    assert dec._box_event_tick == 6 and kinds()[1:] == ["time_next_sweep", "box", "box", "time_next_sweep", "box", "box", "time_next_sweep", "box"]
+    assert [e[2] is r for e, r in zip(dec.box_event_log, recs[0::2])] == [True] * 3 and len(dec.box_event_log) == 3
+    assert [(e[0].cuda_event, e[1].cuda_event) for e in dec.box_event_log] == timed()
+    assert all(e[0].timing and e[1].timing and (e[0].records, e[1].records) == (1, 1) for e in dec.box_event_log)
+
+
+BOX_TICKET = {"kind", "args", "rec", "keep", "tau", "epoch", "host"}
+BAND_TICKET = {"kind", "args", "rec", "tau", "epoch", "host"}
+EXACT_FINE_TICKET = {"kind", "args", "rec", "epoch", "host"}
+TWO_PASS_TICKET = {"coarse", "fine", "lattice", "lattice_host", "vol_hand", "vol_obj"}
+
+
+def test_tickets_are_plain_dicts_with_these_keys(machine, monkeypatch):
+    """Every ticket coarse_begin, fine_begin and two_pass_begin hand out, key by key (reconstruct.py and the GPU tests index them), the
+    scale epoch they carry, one copy of a record to the host behind its own sweep - and none for the repeat inside coarse_finish,
+    whose record is read with .cpu()."""
+    dec, calls = machine
+    tau = dec._box_tau
+    real_copy = dec._record_to_host
+    dec._record_to_host = lambda rec: dec._L.log.append(("copy", None if rec is None else rec.numel())) or real_copy(rec)
+    kinds = lambda: [k if k != "copy" else (k, m) for k, m in dec._L.log]
+    dec._recalibrations = dec._box_epoch = dec._fine_epoch = 2          # (an epoch that is not the initial one)
+    dec._L.script = [good_record(tau) for _ in range(8)]
+    dec._L.log.clear()
+    t = dec.coarse_begin(*ARGS)
+    assert type(t) is dict and set(t) == BOX_TICKET and (t["kind"], t["tau"], t["epoch"]) == ("box", tau, 2) and t["args"] == ARGS + (0, True, True)
+    assert len(t["keep"]) == 2 and t["rec"].numel() == hd.REC_WORDS and kinds() == ["box", ("copy", hd.REC_WORDS)]
+    _, _, t = dec.fine_begin(*ARGS, mc_only=True)
+    assert type(t) is dict and set(t) == BAND_TICKET and (t["kind"], t["tau"], t["epoch"]) == ("band", tau, 2) and t["args"] == ARGS + (0, True, True)
+    _, _, t = dec.fine_begin(*ARGS)
+    assert type(t) is dict and set(t) == EXACT_FINE_TICKET and (t["kind"], t["epoch"]) == ("exact", 2) and t["rec"].numel() == 16
+    dec._fine_epoch = -1
+    dec._L.log.clear()
+    _, _, t = dec.fine_begin(*ARGS, mc_only=True)
+    assert set(t) == EXACT_FINE_TICKET | {"compare", "periodic"} and len(t["compare"]) == 5 and t["periodic"] is False
+    assert kinds() == ["grid", ("copy", 16), "plain"]
+    dec._fine_epoch, dec._fine_compare_in_flight = 2, False
+    dec.set_math("f32")
+    _, _, t = dec.fine_begin(*ARGS, mc_only=True)                     # the fp32 chain leaves no range words: no record
+    assert set(t) == EXACT_FINE_TICKET and t["rec"] is None and t["host"] is None
+    dec.set_math("f16x3")
+    # both passes in one go, one-plane sweeps: sweep, its record, zoom cube, the lattice IN FRONT of the fine sweep, sweep, its record
+    dec._L.log.clear()
+    t = dec.two_pass_begin(N, ARGS[2])
+    assert type(t) is dict and set(t) == TWO_PASS_TICKET and set(t["coarse"]) == BOX_TICKET and set(t["fine"]) == BAND_TICKET
+    assert t["coarse"]["args"] == ARGS + (0, True, True) and t["fine"]["args"] == (N, None, None, 0, True, True)
+    assert (t["coarse"]["epoch"], t["fine"]["epoch"], t["lattice"].dtype, t["lattice"].numel()) == (2, 2, torch.float32, 4)
+    assert kinds() == ["box", ("copy", hd.REC_WORDS), "zoom", ("copy", 4), "band_dev", ("copy", hd.REC_WORDS)]
+    # ... and ordinary sweeps
+    dec.set_fast(False)
+    dec._L.log.clear()
+    since = dec._coarse_since_cal
+    t = dec.two_pass_begin(N, ARGS[2], hand=True, obj=False)
+    assert type(t) is dict and set(t) == TWO_PASS_TICKET and set(t["fine"]) == EXACT_FINE_TICKET and t["vol_obj"] is None
+    assert set(t["coarse"]) == {"kind", "args", "rec", "keep", "epoch", "host"} and t["coarse"]["kind"] == t["fine"]["kind"] == "exact"
+    assert t["coarse"]["args"] == ARGS + (0, True, False) and t["fine"]["args"] == (N, None, None, 0, True, False)
+    assert kinds() == ["grid", ("copy", 16), "zoom", ("copy", 4), "grid_dev", ("copy", 16)] and dec._coarse_since_cal == since
+    assert dec._L.calls[-2][0] == "asdf_zoom_cube" and dec._L.calls[-2][1][3:5] == (1, 0)
+    t = dec.coarse_begin(*ARGS)
+    assert type(t) is dict and set(t) == {"kind", "args", "rec", "keep", "epoch", "recalibrate", "host"} and (t["kind"], t["epoch"], t["recalibrate"]) == ("exact", 2, False)
+    # the repeat of a refused box sweep inside coarse_finish: no "host" entry, no copy enqueued for it
+    dec.set_fast(True)
+    bad = good_record(tau)
+    _listed_box(bad, tau)
+    dec._L.script = [bad]
+    t = dec.coarse_begin(*ARGS)
+    seen = []
+    dec._record_of = lambda ticket: seen.append(ticket) or hd.HipSdfDecoder._record_of(ticket)
+    dec._L.log.clear()
+    dec.coarse_finish(t)
+    assert kinds() == ["grid"] and seen[0] is t and set(seen[1]) == {"kind", "args", "rec", "keep", "epoch"} and seen[1]["kind"] == "exact"
+    assert seen[1]["args"] == t["args"] and seen[1]["epoch"] == 2
