@@ -18,8 +18,9 @@ import time
 import numpy as np
 import torch
 
-from . import _native, synthetic
+from . import synthetic
 from .networks.model import build_decoder
+from .sample_pipeline import pipelined_two_pass
 from .utils import mesh as mesh_utils
 
 
@@ -111,219 +112,6 @@ def npz_code_source(code_dir, device="cuda", on_host=True):
             obj = {"obj_trans": up(np.asarray(z["obj_trans"], dtype=np.float32))}
         return lat, mano, obj
     return source
-
-
-def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_copy=False, label_out=False, midpoint=None, report=None,
-                       fast=None):
-    """Software pipeline over independent samples.  `samples` yields (key, latent, mano_results, obj_results); the
-    generator yields (key, result) in order, where result holds the pass-2 volumes (device), the zoom cube and the
-    marching-cubes output per enabled branch (`verts_*`, `faces_*` device tensors, absent when MC found no surface).
-
-    The pipeline exists to produce meshes: it runs the coarse pass through `coarse_begin` / `coarse_finish` and the fine pass
-    through `fine_begin(..., mc_only=True)`.  By default (round 6) both are ORDINARY sweeps: every voxel of both lattices in the
-    reference's arithmetic class (<= 1e-5).  `fast=True` (or ASDF_FAST=1 / `--fast`; `fast=None` leaves the decoder as it is
-    configured) opts in to the audited one-plane sweeps wherever the decoder supports them - the yielded `vol_*` are then exact only
-    where marching cubes reads values and must not be used as SDF volumes.
-
-    Per sample the GPU work is  pass 1 -> [64-byte bbox readback, zoom cube on the host] -> pass 2 -> marching cubes,
-    and only the bracketed step and the MC size readbacks synchronise with the host.  Pass 1 of sample k+1 is queued
-    right behind pass 2 of sample k, i.e. before sample k's marching cubes and before the consumer's host work
-    (D2H copy, component filter, PLY export), so the GPU never waits for the host between samples.
-
-    host_copy=True additionally runs the largest-component filter (K8) behind each marching cubes and copies its result
-    to pinned host memory on a side stream (`host_kept_verts_*`, `host_kept_faces_*` at input capacity, `host_kept_counts_*`
-    = kept vertices / faces, valid after `copy_done_*`.synchronize(); with label_out also the whole surface as
-    `host_verts_hand` / `host_faces_hand`): a plain `.cpu()` on the compute stream would wait behind the NEXT sample's
-    queued passes.
-
-    label_out=True runs the label pass (utils/mesh.py:137-157) over the hand mesh vertices right behind the hand's
-    marching cubes (`labels_hand`, int64 device tensor; `host_labels_hand` with host_copy).  The decoder holds one
-    sample's folded constants at a time, so sample k is re-bound for it and sample k+1 bound again afterwards.
-
-    midpoint(key, result), if given, is called for sample k between queuing pass 2 of sample k+1 and pass 1 of sample
-    k+2: GPU work it enqueues (the eval-mode ICP of sample k's hand mesh) lands between two decoder passes instead of
-    behind both, and its host part is covered by the pass that is already running.
-
-    report, if given (a dict), receives the evaluator that ran and a snapshot of its sweep counters (see write_sweeps_json)."""
-    from .marching_cubes import marching_cubes_begin, marching_cubes_finish
-    from .utils.mesh import GRID_MODES, zoom_cube_from_bboxes
-    from .utils.utils import bind_sample, decoder_for
-    it = iter(samples)
-    cur = next(it, None)
-    if cur is None:
-        return
-    hip = decoder_for(decoder, specs, cur[2])      # the HIP kernels, or the module on PyTorch-ROCm for variants they do not cover
-    if fast is not None and hasattr(hip, "set_fast"):
-        hip.set_fast(bool(fast))
-    if report is not None:                         # (the caller's `sweeps.json`: which evaluator ran, and its counters at the start)
-        report["evaluator"], report["snapshot"] = hip, hip.sweep_snapshot()
-    hb, ob = specs.get("HandBranch", True), specs.get("ObjectBranch", True)
-    mode = GRID_MODES[grid_mode]
-    voxel = 2.0 / (N - 1)
-    copy_stream = torch.cuda.Stream(device=hip.device) if host_copy else None
-
-    def bind(sample):
-        _, latent, mano, obj = sample
-        bind_sample(hip, specs, latent, mano, obj)
-
-    def to_host(r, key, t):
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream(hip.device))
-        h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-        with torch.cuda.stream(copy_stream):
-            copy_stream.wait_event(ready)
-            h.copy_(t, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(copy_stream)
-        t.record_stream(copy_stream)
-        r["host_" + key] = h
-        return done
-
-    # Round 5 (VERDICT r04 item 4): wherever the decoder's state allows it (HipSdfDecoder.can_speculate: both one-plane modes on, both
-    # whole-lattice comparisons valid, none due) a sample is ENQUEUED IN ONE GO - coarse box sweep, zoom cube on the device, narrow-band
-    # fine sweep on that lattice, marching-cubes counts and a capacity-bounded emit - and the host only reads records afterwards: no
-    # host round trip between the coarse and the fine pass, none between count and emit.  A refused sweep is repeated step by step, as
-    # before.  ASDF_SPECULATE=0 keeps every sample on the step-by-step path.
-    speculate = os.environ.get("ASDF_SPECULATE", "1") != "0" and hasattr(hip, "two_pass_begin")
-    seen = {}            # part -> (most vertices, most faces) of the surfaces so far: sizes the next sample's emit buffers
-
-    def capacity(part):
-        c = seen.get(part)
-        return None if c is None else (int(1.5 * c[0]) + 4096, int(1.5 * c[1]) + 8192)
-
-    def first_pass(sample):
-        bind(sample)
-        t = hip.two_pass_begin(N, voxel, mode, hand=hb, obj=ob) if speculate else None
-        if t is None:
-            return hip.coarse_begin(N, [-1.0, -1.0, -1.0], voxel, mode, hand=hb, obj=ob)
-        # marching cubes right behind the fine pass - count AND capacity-bounded emit - once the sizes of earlier surfaces are known.
-        # (Never the count alone: its emit would run when the sample is finished, after the NEXT sample's count phase has reused the
-        # workspace - found as a memory fault at N = 128.  Without sizes to go by the sample's marching cubes waits for surfaces().)
-        parts = [(slot, part) for slot, (part, on) in enumerate((("hand", hb), ("obj", ob))) if on]
-        t["mc"] = ({part: marching_cubes_begin(t["vol_" + part], 0.0, slot, capacity=capacity(part)) for slot, part in parts}
-                   if all(capacity(part) is not None for _, part in parts) else None)
-        return t
-
-    def second_pass(ticket, judged=None):
-        if "coarse" in ticket and judged is None:
-            # both passes are in flight already: nothing to launch, and nothing is READ here either - the records are judged when the
-            # sample is finished (surfaces), so the host never waits in the middle of the previous sample's post-processing
-            return {"pending": ticket}
-        if "coarse" in ticket:
-            b = hip.coarse_finish(ticket["coarse"], judged=judged)      # refused: an ordinary sweep now (the decoder is bound to this sample)
-        else:
-            # waits for pass 1 (the zoom cube is data dependent); a coarse sweep whose guards fired (fp16 range, or the error
-            # check of the box-only sweep) is repeated in there - the decoder is still bound to this sample
-            b = hip.coarse_finish(ticket)
-        boxes = ([_native.box_of(b, 0)] if hb else []) + ([_native.box_of(b, 1)] if ob else [])
-        nvs, norg = zoom_cube_from_bboxes(boxes, N, voxel)
-        # the fine pass carries a guard record (fp16 range report; error check of the narrow-band sweep): read behind the
-        # marching-cubes size read-back in surfaces().  The volumes go to marching cubes only (mc_only).
-        vh, vo, ticket = hip.fine_begin(N, norg.tolist(), nvs.item(), mode, hand=hb, obj=ob, mc_only=True)
-        return {"vol_hand": vh, "vol_obj": vo, "voxel_size": nvs, "origin": norg.tolist(), "bbox": b, "fine_ticket": ticket}
-
-    def surfaces(r, sample, between=None):
-        """Marching cubes (and the label pass) of one sample.  between(rebound), if given, is called once the marching-cubes
-        launches are queued and before the component filter, label pass and host copies are: the caller queues pass 2 of the
-        next sample there (it may overwrite the volumes only behind the emits), so the ~40 small launches of the post-processing
-        never sit between a pass-1 read-back and the pass-2 launch (eval-mode trace: 1.3 ms of idle GPU per sample).  `rebound`
-        tells it whether the decoder was re-bound to this sample."""
-        rebound = False
-        spec = r.pop("pending", None)
-        if spec is not None:
-            # a sample that was enqueued in one go: judge its coarse record now (everything of it has long run).  Accepted - the usual
-            # case - means the fine pass ran on exactly the lattice the host arithmetic gives for these boxes (asdf_zoom_cube).
-            judged = hip.coarse_judge(spec["coarse"])
-            if judged[0]:
-                origin, nvs = hip.lattice_of(spec)
-                r.update({"vol_hand": spec["vol_hand"], "vol_obj": spec["vol_obj"], "voxel_size": nvs, "origin": origin, "bbox": judged[1],
-                          "fine_ticket": spec["fine"], "mc_tickets": spec["mc"]})
-            else:
-                bind(sample)                       # refused: this sample again, step by step
-                rebound = True
-                r.update(second_pass(spec, judged=judged))
-        ticket = r.pop("fine_ticket", None)
-
-        def begin_counts():
-            # count phases of both volumes (no host synchronisation)
-            return {part: marching_cubes_begin(r["vol_" + part], 0.0, slot) for slot, (part, on) in enumerate((("hand", hb), ("obj", ob))) if on}
-
-        # the count phases are queued BEFORE the fine pass's guard record is read (it is accepted all but never refused): one
-        # host wait then covers the record and the sizes, instead of record -> launch -> sizes with the GPU idle in between
-        # (a sample enqueued in one go brings its marching-cubes tickets along: counted, and usually emitted, behind its fine pass)
-        tickets = r.pop("mc_tickets", None) or begin_counts()
-        while hip.fine_needs_repeat(ticket):
-            # pass 2 left the fp16 range (the decoder has been re-calibrated, or switched to the fp32 kernel) or its
-            # narrow-band form was not accepted: repeat this sample's pass 2 - and its count phases
-            bind(sample)
-            rebound = True
-            r["vol_hand"], r["vol_obj"], ticket = hip.fine_begin(N, r["origin"], float(r["voxel_size"]), mode, hand=hb, obj=ob, mc_only=True)
-            tickets = begin_counts()
-        for part, on in (("hand", hb), ("obj", ob)):
-            r["V_" + part] = r["F_" + part] = 0
-            if on:
-                try:
-                    v, f = marching_cubes_finish(tickets[part])
-                except (ValueError, RuntimeError) as e:         # the reference logs and skips (utils/mesh.py:353-358)
-                    r["mc_error_" + part] = str(e)
-                    continue
-                r["verts_" + part], r["faces_" + part] = v, f
-                r["V_" + part], r["F_" + part] = v.shape[0], f.shape[0]
-                c = seen.get(part, (0, 0))
-                seen[part] = (max(c[0], v.shape[0]), max(c[1], f.shape[0]))
-        if between is not None:
-            between(rebound)
-        for part, on in (("hand", hb), ("obj", ob)):
-            if on and "verts_" + part in r:
-                v, f = r["verts_" + part], r["faces_" + part]
-                if label_out and part == "hand":
-                    # the vertex arithmetic of utils/mesh.py:138-141 in fp32, on the device
-                    pts = v * float(r["voxel_size"]) + torch.tensor(r["origin"], dtype=torch.float32, device=v.device)
-                    bind(sample)
-                    r["labels_hand"] = hip.classify_points(pts, want_sdf=False)[3]
-                if host_copy:
-                    # K8 right behind marching cubes: only the largest component (what the file holds) crosses to the
-                    # host, plus the whole surface when the label pass needs every vertex
-                    from .mesh_post import keep_largest_component_device
-                    kv, kf, counts = keep_largest_component_device(v, f, r["voxel_size"], r["origin"])
-                    r["kept_dev_" + part] = (kv, kf, counts)       # (the eval-mode hook samples the kept surface on the device)
-                    to_host(r, "kept_verts_" + part, kv)
-                    to_host(r, "kept_faces_" + part, kf)
-                    done = to_host(r, "kept_counts_" + part, counts)
-                    if "labels_" + part in r:
-                        to_host(r, "verts_" + part, v)
-                        to_host(r, "faces_" + part, f)
-                        done = to_host(r, "labels_" + part, r["labels_" + part])
-                    r["copy_done_" + part] = done           # the side stream is in order: the last event covers all
-
-    r = second_pass(first_pass(cur))
-    nxt = next(it, None)
-    bbox_next = first_pass(nxt) if nxt is not None else None
-    while True:
-        if nxt is not None:
-            queued = []
-
-            def queue_next_pass2(rebound):
-                if rebound:
-                    bind(nxt)
-                queued.append(second_pass(bbox_next))
-
-            # fetch sample k+2 while the queue is short: a source that uploads its codes with a blocking copy would
-            # otherwise sit behind pass 2 of sample k+1 and hold the consumer back for a whole pass
-            after = next(it, None)
-            surfaces(r, cur, queue_next_pass2)          # MC of sample k, queued behind pass 1 of sample k+1
-            r_next = queued[0]
-            if midpoint is not None:
-                midpoint(cur[0], r)
-            bbox_after = first_pass(after) if after is not None else None
-        else:
-            surfaces(r, cur)
-            if midpoint is not None:
-                midpoint(cur[0], r)
-        yield cur[0], r
-        if nxt is None:
-            return
-        cur, r, nxt, bbox_next = nxt, r_next, after, bbox_after
 
 
 _gt_proc = None

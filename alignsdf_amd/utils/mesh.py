@@ -52,14 +52,20 @@ def zoom_cube_from_bboxes(bboxes, N, voxel_size):
     return new_voxel_size, new_origin
 
 
+def zoom_cube_of_record(record, hand_branch, obj_branch, N, voxel_size):
+    """The zoom cube of a box / sweep record (the hand's box at head 0, the object's at head 1).  A branch that is switched off is not
+    used for the zoom cube (utils/mesh.py:239-247)."""
+    boxes = [_native.box_of(record, head) for head, on in enumerate((hand_branch, obj_branch)) if on]
+    return zoom_cube_from_bboxes(boxes, N, voxel_size)
+
+
 def get_higher_res_cube(hand_branch, obj_branch, sdf_values_hand, sdf_values_obj, N, voxel_origin, voxel_size):
     """Zoom cube around the negative voxels of the enabled branches (utils/mesh.py:198-256)."""
-    boxes = []
-    for on, vol in ((hand_branch, sdf_values_hand), (obj_branch, sdf_values_obj)):
+    record = np.zeros(_native.BOX_WORDS, dtype=np.int32)
+    for head, (on, vol) in enumerate(((hand_branch, sdf_values_hand), (obj_branch, sdf_values_obj))):
         if on:
-            b = neg_bbox(vol)
-            boxes.append(_native.box_of(b, 0))
-    return zoom_cube_from_bboxes(boxes, N, voxel_size)
+            record[_native.BOX_STRIDE * head:][:_native.BOX_RANGE] = neg_bbox(vol)
+    return zoom_cube_of_record(record, hand_branch, obj_branch, N, voxel_size)
 
 
 def place_vertices(verts_d, faces_d, voxel_grid_origin, voxel_size, offset=None, scale=None):
@@ -270,12 +276,7 @@ def decode_two_pass(hand_branch, obj_branch, decoder, latent_vec, mano_results, 
     # coarse pass: consumed only through its boxes (ordinary sweep, or the box-only sweep when the decoder is set to it);
     # a sweep whose range / error guards fired is repeated inside coarse_finish
     b = hip.coarse_finish(hip.coarse_begin(N, [-1.0, -1.0, -1.0], voxel_size, mode, hand=hand_branch, obj=obj_branch))
-    boxes = []
-    if hand_branch:
-        boxes.append(_native.box_of(b, 0))
-    if obj_branch:
-        boxes.append(_native.box_of(b, 1))
-    new_voxel_size, new_origin = zoom_cube_from_bboxes(boxes, N, voxel_size)
+    new_voxel_size, new_origin = zoom_cube_of_record(b, hand_branch, obj_branch, N, voxel_size)
     # fine pass: an ordinary sweep (range report through its bbox record), or - when the decoder is set to it and the caller
     # declares that the volumes go to marching cubes only - the narrow-band sweep; either is repeated if its guards fired
     for _ in range(6):

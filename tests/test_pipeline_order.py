@@ -1,4 +1,4 @@
-"""Order of the launches pipelined_two_pass issues (alignsdf_amd/reconstruct.py), checked on the CPU with a recording stand-in for
+"""Order of the launches pipelined_two_pass issues (alignsdf_amd/sample_pipeline.py), checked on the CPU with a recording stand-in for
 the decoder: per sample  pass 1 -> [box read-back] -> pass 2 -> marching cubes (utils/mesh.py:27-121, 351-369), with pass 1 of the
 next sample queued ahead of this sample's marching cubes, pass 2 of the next sample ahead of this sample's post-processing (label
 pass), the eval hook between pass 2 of k+1 and pass 1 of k+2 - and a refused fine sweep repeated before marching cubes reads it."""
@@ -47,15 +47,31 @@ def harness(monkeypatch):
     log = []
     state = {}
 
-    def install(refuse=(), cls=RecordingDecoder, **kw):
+    def install(refuse=(), cls=RecordingDecoder, trace=False, **kw):
+        """trace=True: the log is the complete call trace - every bind_sample as ("bind", k), and every marching_cubes_begin as ONE
+        event with its slot and capacity, ("mc_begin", k, volume, slot, capacity), instead of the count / bounded-emit pair."""
         dec = cls(log, refuse, **kw)
         state["dec"] = dec
         import alignsdf_amd.marching_cubes as mc
         import alignsdf_amd.utils.utils as uu
+
+        def bind(hip, specs, latent, mano, obj):
+            hip.bound = int(latent)
+            if trace:
+                log.append(("bind", hip.bound))
+
+        def mc_begin(vol, level, slot, capacity=None):
+            if trace:
+                log.append(("mc_begin", vol[1], vol[0], slot, capacity))
+            else:
+                log.append(("mc_count", vol[1], vol[0]))
+                if capacity:
+                    log.append(("mc_emit_bounded", vol[1], vol[0], capacity))
+            return vol
+
         monkeypatch.setattr(uu, "decoder_for", lambda decoder, specs, mano: dec)
-        monkeypatch.setattr(uu, "bind_sample", lambda hip, specs, latent, mano, obj: setattr(hip, "bound", int(latent)))
-        monkeypatch.setattr(mc, "marching_cubes_begin", lambda vol, level, slot, capacity=None: (
-            log.append(("mc_count", vol[1], vol[0])), log.append(("mc_emit_bounded", vol[1], vol[0], capacity)) if capacity else None, vol)[2])
+        monkeypatch.setattr(uu, "bind_sample", bind)
+        monkeypatch.setattr(mc, "marching_cubes_begin", mc_begin)
         monkeypatch.setattr(mc, "marching_cubes_finish", lambda t: (log.append(("mc_emit", t[1], t[0])),
                                                                    (torch.zeros(6, 3), torch.zeros(8, 3, dtype=torch.int32)))[1])
         return dec
@@ -225,3 +241,94 @@ def test_speculation_can_be_switched_off(harness, monkeypatch):
     monkeypatch.setenv("ASDF_SPECULATE", "0")
     out = list(rc.pipelined_two_pass(object(), SPECS, samples(3), 16))
     assert [k for k, _ in out] == [0, 1, 2] and not [e for e in log if e[0] in ("zoom_dev", "judge")]
+
+
+# ---- the complete call trace, recorded from the pipeline as it stood before it moved to sample_pipeline.py -------------------------
+OBJ_ONLY = {"HandBranch": False, "ObjectBranch": True}
+B = dict(cls=SpeculatingDecoder, n=4, stepwise=(0,), refuse=(3,), refuse_coarse_of=(2,), label_out=True, hook=True)
+SCENARIOS = {
+    "A": dict(cls=RecordingDecoder, n=3, refuse=(1,), label_out=True, hook=True),
+    "B": B,
+    "C": dict(cls=SpeculatingDecoder, n=3, stepwise=(0,), specs=OBJ_ONLY),
+    "C_hook": dict(cls=SpeculatingDecoder, n=3, stepwise=(0,), specs=OBJ_ONLY, hook=True),
+    "D_empty": dict(cls=RecordingDecoder, n=0, hook=True),
+    "D_one": dict(cls=RecordingDecoder, n=1, hook=True),
+    "E": dict(B, env={"ASDF_SPECULATE": "0"}),
+}
+
+
+def run_scenario(harness, monkeypatch, cls, n, specs=SPECS, label_out=False, hook=False, env=None, **kw):
+    """(the whole log, the sorted keys of every result at the moment it is yielded)"""
+    log, install = harness
+    install(cls=cls, trace=True, **kw)
+    for name, value in (env or {}).items():
+        monkeypatch.setenv(name, value)
+    midpoint = (lambda key, r: log.append(("hook", key))) if hook else None
+    keys = [(k, sorted(r)) for k, r in rc.pipelined_two_pass(object(), specs, samples(n), 16, label_out=label_out, midpoint=midpoint)]
+    assert [k for k, _ in keys] == list(range(n))
+    return log, [ks for _, ks in keys]
+
+
+KEYS_LABELLED = ["F_hand", "F_obj", "V_hand", "V_obj", "bbox", "faces_hand", "faces_obj", "labels_hand", "origin", "verts_hand",
+                 "verts_obj", "vol_hand", "vol_obj", "voxel_size"]
+KEYS_OBJ_ONLY = ["F_hand", "F_obj", "V_hand", "V_obj", "bbox", "faces_obj", "origin", "verts_obj", "vol_hand", "vol_obj", "voxel_size"]
+KEYS_BOTH = ["F_hand", "F_obj", "V_hand", "V_obj", "bbox", "faces_hand", "faces_obj", "origin", "verts_hand", "verts_obj", "vol_hand",
+             "vol_obj", "voxel_size"]
+RECORDED = {           # scenario -> (the whole log, the sorted keys of every yielded result)
+    "A": ([
+        ("bind", 0), ("pass1", 0), ("boxes", 0), ("pass2", 0), ("bind", 1), ("pass1", 1), ("mc_begin", 0, "vol_hand", 0, None),
+        ("mc_begin", 0, "vol_obj", 1, None), ("mc_emit", 0, "vol_hand"), ("mc_emit", 0, "vol_obj"), ("boxes", 1), ("pass2", 1),
+        ("bind", 0), ("labels", 0), ("hook", 0), ("bind", 2), ("pass1", 2), ("mc_begin", 1, "vol_hand", 0, None),
+        ("mc_begin", 1, "vol_obj", 1, None), ("bind", 1), ("pass2", 1), ("mc_begin", 1, "vol_hand", 0, None),
+        ("mc_begin", 1, "vol_obj", 1, None), ("mc_emit", 1, "vol_hand"), ("mc_emit", 1, "vol_obj"), ("bind", 2), ("boxes", 2),
+        ("pass2", 2), ("bind", 1), ("labels", 1), ("hook", 1), ("mc_begin", 2, "vol_hand", 0, None),
+        ("mc_begin", 2, "vol_obj", 1, None), ("mc_emit", 2, "vol_hand"), ("mc_emit", 2, "vol_obj"), ("bind", 2), ("labels", 2),
+        ("hook", 2)], KEYS_LABELLED),
+    "B": ([
+        ("bind", 0), ("pass1", 0), ("boxes", 0), ("pass2", 0), ("bind", 1), ("pass1", 1), ("zoom_dev", 1), ("pass2", 1),
+        ("mc_begin", 0, "vol_hand", 0, None), ("mc_begin", 0, "vol_obj", 1, None), ("mc_emit", 0, "vol_hand"),
+        ("mc_emit", 0, "vol_obj"), ("bind", 0), ("labels", 0), ("hook", 0), ("bind", 2), ("pass1", 2), ("zoom_dev", 2), ("pass2", 2),
+        ("mc_begin", 2, "vol_hand", 0, (4105, 8204)), ("mc_begin", 2, "vol_obj", 1, (4105, 8204)), ("judge", 1),
+        ("mc_begin", 1, "vol_hand", 0, None), ("mc_begin", 1, "vol_obj", 1, None), ("mc_emit", 1, "vol_hand"),
+        ("mc_emit", 1, "vol_obj"), ("bind", 1), ("labels", 1), ("hook", 1), ("bind", 3), ("pass1", 3), ("zoom_dev", 3), ("pass2", 3),
+        ("mc_begin", 3, "vol_hand", 0, (4105, 8204)), ("mc_begin", 3, "vol_obj", 1, (4105, 8204)), ("judge", 2), ("bind", 2),
+        ("pass1_again", 2), ("boxes", 2), ("pass2", 2), ("mc_begin", 2, "vol_hand", 0, None), ("mc_begin", 2, "vol_obj", 1, None),
+        ("mc_emit", 2, "vol_hand"), ("mc_emit", 2, "vol_obj"), ("bind", 3), ("bind", 2), ("labels", 2), ("hook", 2), ("judge", 3),
+        ("bind", 3), ("pass2", 3), ("mc_begin", 3, "vol_hand", 0, None), ("mc_begin", 3, "vol_obj", 1, None),
+        ("mc_emit", 3, "vol_hand"), ("mc_emit", 3, "vol_obj"), ("bind", 3), ("labels", 3), ("hook", 3)], KEYS_LABELLED),
+    "C": ([
+        ("bind", 0), ("pass1", 0), ("boxes", 0), ("pass2", 0), ("bind", 1), ("pass1", 1), ("zoom_dev", 1), ("pass2", 1),
+        ("mc_begin", 0, "vol_obj", 1, None), ("mc_emit", 0, "vol_obj"), ("bind", 2), ("pass1", 2), ("zoom_dev", 2), ("pass2", 2),
+        ("mc_begin", 2, "vol_obj", 1, (4105, 8204)), ("judge", 1), ("mc_begin", 1, "vol_obj", 1, None), ("mc_emit", 1, "vol_obj"),
+        ("judge", 2), ("mc_emit", 2, "vol_obj")], KEYS_OBJ_ONLY),
+    "C_hook": ([
+        ("bind", 0), ("pass1", 0), ("boxes", 0), ("pass2", 0), ("bind", 1), ("pass1", 1), ("zoom_dev", 1), ("pass2", 1),
+        ("mc_begin", 0, "vol_obj", 1, None), ("mc_emit", 0, "vol_obj"), ("hook", 0), ("bind", 2), ("pass1", 2), ("zoom_dev", 2),
+        ("pass2", 2), ("mc_begin", 2, "vol_obj", 1, (4105, 8204)), ("judge", 1), ("mc_begin", 1, "vol_obj", 1, None),
+        ("mc_emit", 1, "vol_obj"), ("hook", 1), ("judge", 2), ("mc_emit", 2, "vol_obj"), ("hook", 2)], KEYS_OBJ_ONLY),
+    "D_empty": ([], None),
+    "D_one": ([
+        ("bind", 0), ("pass1", 0), ("boxes", 0), ("pass2", 0), ("mc_begin", 0, "vol_hand", 0, None),
+        ("mc_begin", 0, "vol_obj", 1, None), ("mc_emit", 0, "vol_hand"), ("mc_emit", 0, "vol_obj"), ("hook", 0)], KEYS_BOTH),
+    "E": ([
+        ("bind", 0), ("pass1", 0), ("boxes", 0), ("pass2", 0), ("bind", 1), ("pass1", 1), ("mc_begin", 0, "vol_hand", 0, None),
+        ("mc_begin", 0, "vol_obj", 1, None), ("mc_emit", 0, "vol_hand"), ("mc_emit", 0, "vol_obj"), ("boxes", 1), ("pass2", 1),
+        ("bind", 0), ("labels", 0), ("hook", 0), ("bind", 2), ("pass1", 2), ("mc_begin", 1, "vol_hand", 0, None),
+        ("mc_begin", 1, "vol_obj", 1, None), ("mc_emit", 1, "vol_hand"), ("mc_emit", 1, "vol_obj"), ("boxes", 2), ("pass2", 2),
+        ("bind", 1), ("labels", 1), ("hook", 1), ("bind", 3), ("pass1", 3), ("mc_begin", 2, "vol_hand", 0, None),
+        ("mc_begin", 2, "vol_obj", 1, None), ("mc_emit", 2, "vol_hand"), ("mc_emit", 2, "vol_obj"), ("boxes", 3), ("pass2", 3),
+        ("bind", 2), ("labels", 2), ("hook", 2), ("mc_begin", 3, "vol_hand", 0, None), ("mc_begin", 3, "vol_obj", 1, None),
+        ("bind", 3), ("pass2", 3), ("mc_begin", 3, "vol_hand", 0, None), ("mc_begin", 3, "vol_obj", 1, None),
+        ("mc_emit", 3, "vol_hand"), ("mc_emit", 3, "vol_obj"), ("bind", 3), ("labels", 3), ("hook", 3)], KEYS_LABELLED),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SCENARIOS))
+def test_call_trace_is_the_recorded_one(harness, monkeypatch, name):
+    """Every call the pipeline makes - bind_sample, the decoder, marching cubes with slot and capacity, the label pass, the hook - in
+    order, and what a result holds when it is yielded: equal to what the pipeline did before it was restructured.  (Scenario C without
+    a hook has 20 events; C_hook, the same with the midpoint hook, the 23 of the issue that asked for this test.)"""
+    log, keys = run_scenario(harness, monkeypatch, **SCENARIOS[name])
+    want_log, want_keys = RECORDED[name]
+    assert log == want_log
+    assert all(k == want_keys for k in keys)
