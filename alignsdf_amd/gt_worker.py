@@ -1,5 +1,5 @@
 """Ground-truth sampling worker process of eval mode (`python -m alignsdf_amd.gt_worker`, started by
-reconstruct.GroundTruthPrefetcher).  The reference reads one ground-truth mesh per sample and samples 30 000 points from it
+gt_prefetch.GroundTruthPrefetcher).  The reference reads one ground-truth mesh per sample and samples 30 000 points from it
 (utils/mesh.py:386-389, deep_sdf/metrics/icp_trans_scale.py:19-23); here that is numpy-only work in a process of its own, so that
 15 ms of parsing per sample never holds the interpreter lock of the process that launches the decoder passes.
 

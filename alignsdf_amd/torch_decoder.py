@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _native
+from .code_sources import CodeUploader
 
 CHUNK = 2 ** 18          # max_batch of reconstruct.py:93
 
@@ -165,7 +166,6 @@ class TorchModuleDecoder:
             t = t.detach()
             if t.device.type == "cpu" and self.device.type == "cuda":
                 if getattr(self, "_uploader", None) is None:
-                    from .reconstruct import CodeUploader
                     self._uploader = CodeUploader(self.device)
                 return self._uploader(t.to(torch.float32).numpy())
             return t.to(self.device)

@@ -86,15 +86,6 @@ def place_vertices(verts_d, faces_d, voxel_grid_origin, voxel_size, offset=None,
     return verts, faces, mesh_points
 
 
-def extract_surface(sdf, voxel_grid_origin, voxel_size, offset=None, scale=None):
-    """MC on the device + place_vertices.  Raises like skimage on failure."""
-    vol = sdf if isinstance(sdf, torch.Tensor) else torch.as_tensor(np.asarray(sdf))
-    if not vol.is_cuda:
-        vol = vol.cuda()
-    verts_d, faces_d = marching_cubes_device(vol, 0.0)
-    return place_vertices(verts_d, faces_d, voxel_grid_origin, voxel_size, offset, scale)
-
-
 def ground_truth_mesh_path(ply_filename_out, task, data_root="data"):
     """Where the reference looks for the ground-truth mesh of an output file (utils/mesh.py:386-388):
     <data_root>/<task>/test/mesh_<hand|obj>/<sample id>.obj."""
@@ -103,13 +94,36 @@ def ground_truth_mesh_path(ply_filename_out, task, data_root="data"):
     return os.path.join(data_root, task, "test", mesh_dir, gt_mesh_name)
 
 
-def begin_mesh(mesh_points, faces, ply_filename_out, eval_mode=False, task="obman", data_root="data", allow_missing_gt=False):
-    """First half of utils/mesh.py:383-397 for the placed vertices of the (already filtered) surface: in eval mode sample
-    both meshes and ENQUEUE the translate+scale ICP (K7) against the ground-truth mesh without waiting for it.
-    Returns a ticket for end_mesh.  A missing ground-truth file aborts like the reference (its trimesh.load raises at
-    utils/mesh.py:389) - a wrong data_root must not produce a full run of silently unaligned meshes; with
-    allow_missing_gt the mesh is written unaligned and the caller records `icp_skipped`."""
-    out_v, out_f = mesh_points, faces
+def apply_icp(job, points):
+    """Wait for the eval-mode ICP enqueued for a surface (icp.start_alignment / start_alignment_device) and apply it to its placed
+    vertices.  Returns (points, trans [1,3], scale [1]); without a job the points as they are and zeros / one, like the reference
+    outside eval mode."""
+    if job is None:
+        return points, np.array([0, 0, 0]), np.array([1])
+    from ..icp import finish_icp
+    r = finish_icp(job, points)
+    return r["vertices"], np.asarray(r["all_trans"]).reshape(1, 3), np.asarray(r["all_scale"]).reshape(1)
+
+
+def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, eval_mode=False,
+                   task="obman", largest_component=True, data_root="data", kept=None, allow_missing_gt=False):
+    """The host tail of convert_sdf_samples_to_ply for an already extracted surface (utils/mesh.py:360-397): place_vertices, the
+    largest-component filter, in eval mode the translate+scale ICP (K7) against the ground-truth mesh, export.
+    Returns (verts, faces, trans, scale).  `kept` = (verts, faces) of the largest component in lattice units when the caller has
+    already run the device filter; otherwise the surface is filtered here on the device (K8; host arrays are uploaded for it -
+    there is no host implementation in the product).  A missing ground-truth file aborts like the reference (its trimesh.load
+    raises at utils/mesh.py:389) - a wrong data_root must not produce a full run of silently unaligned meshes; with
+    allow_missing_gt the mesh is written unaligned."""
+    if kept is None and largest_component:
+        vd = verts_d if isinstance(verts_d, torch.Tensor) else torch.as_tensor(np.asarray(verts_d))
+        fd = faces_d if isinstance(faces_d, torch.Tensor) else torch.as_tensor(np.asarray(faces_d))
+        kv, kf, counts = keep_largest_component_device(vd.cuda().float(), fd.cuda().int(), voxel_size, voxel_grid_origin)
+        c = counts.cpu().numpy()                   # (synchronises)
+        kept = kv[:c[0]], kf[:c[1]]
+    verts, faces, out_v = place_vertices(verts_d, faces_d, voxel_grid_origin, voxel_size, offset, scale)
+    out_f = faces
+    if kept is not None:
+        _, out_f, out_v = place_vertices(kept[0], kept[1], voxel_grid_origin, voxel_size, offset, scale)
     job = None
     if eval_mode:
         gt_path = ground_truth_mesh_path(ply_filename_out, task, data_root)
@@ -122,68 +136,11 @@ def begin_mesh(mesh_points, faces, ply_filename_out, eval_mode=False, task="obma
         else:
             raise FileNotFoundError("eval_mode: ground-truth mesh %s not found (data_root=%r); pass allow_missing_gt to write "
                                     "unaligned meshes instead" % (gt_path, data_root))
-    return out_v, out_f, job, ply_filename_out
-
-
-def end_mesh(ticket):
-    """Second half: wait for the ICP (if any), apply it, export.  Returns (trans [3], scale [1]) like the reference
-    (zeros / one outside eval mode)."""
-    out_v, out_f, job, ply_filename_out = ticket
-    trans, scale = np.array([0, 0, 0]), np.array([1])
-    if job is not None:
-        from ..icp import finish_icp
-        r = finish_icp(job, out_v)
-        out_v = r["vertices"]
-        trans, scale = np.asarray(r["all_trans"]).reshape(1, 3), np.asarray(r["all_scale"]).reshape(1)
+    out_v, trans, sc = apply_icp(job, out_v)
     if ply_filename_out:
         os.makedirs(os.path.dirname(os.path.abspath(ply_filename_out)), exist_ok=True)
         write_ply(ply_filename_out, out_v, out_f)
-    return trans, scale
-
-
-def finish_mesh(mesh_points, faces, ply_filename_out, eval_mode=False, task="obman", data_root="data", allow_missing_gt=False):
-    """utils/mesh.py:383-397 for the placed vertices of the (already filtered) surface: in eval mode align it to the
-    ground-truth mesh with the translate+scale ICP (K7); export.  Returns (trans [3], scale [1])."""
-    return end_mesh(begin_mesh(mesh_points, faces, ply_filename_out, eval_mode, task, data_root, allow_missing_gt))
-
-
-def filter_surface_device(verts_d, faces_d, voxel_grid_origin, voxel_size):
-    """K8 on a device surface: (kept lattice verts, kept faces) as device tensors.  Synchronises (it reads the counts)."""
-    kv, kf, counts = keep_largest_component_device(verts_d, faces_d, voxel_size, voxel_grid_origin)
-    c = counts.cpu().numpy()
-    return kv[:c[0]], kf[:c[1]]
-
-
-def begin_export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None,
-                         eval_mode=False, task="obman", largest_component=True, data_root="data", kept=None, allow_missing_gt=False):
-    """place_vertices + the largest-component filter + begin_mesh: everything of the host tail up to (and including)
-    enqueuing the eval-mode ICP.  `kept` = (verts, faces) of the largest component in lattice units when the caller has
-    already run the device filter (the sample pipeline does, right behind marching cubes); otherwise the surface is
-    filtered here on the device (K8; host arrays are uploaded for it - there is no host implementation in the product)."""
-    if kept is None and largest_component:
-        vd = verts_d if isinstance(verts_d, torch.Tensor) else torch.as_tensor(np.asarray(verts_d))
-        fd = faces_d if isinstance(faces_d, torch.Tensor) else torch.as_tensor(np.asarray(faces_d))
-        kept = filter_surface_device(vd.cuda().float(), fd.cuda().int(), voxel_grid_origin, voxel_size)
-    verts, faces, mesh_points = place_vertices(verts_d, faces_d, voxel_grid_origin, voxel_size, offset, scale)
-    if kept is not None:
-        _, kept_faces, kept_points = place_vertices(kept[0], kept[1], voxel_grid_origin, voxel_size, offset, scale)
-        return verts, faces, begin_mesh(kept_points, kept_faces, ply_filename_out, eval_mode, task, data_root, allow_missing_gt)
-    return verts, faces, begin_mesh(mesh_points, faces, ply_filename_out, eval_mode, task, data_root, allow_missing_gt)
-
-
-def end_export_surface(pending):
-    """Wait for the ICP of begin_export_surface (if any), write the file.  Returns (verts, faces, trans, scale)."""
-    verts, faces, ticket = pending
-    trans, sc = end_mesh(ticket)
     return verts, faces, trans, sc
-
-
-def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, eval_mode=False,
-                   task="obman", largest_component=True, data_root="data", kept=None, allow_missing_gt=False):
-    """The host tail of convert_sdf_samples_to_ply for an already extracted surface (utils/mesh.py:360-397).
-    Returns (verts, faces, trans, scale)."""
-    return end_export_surface(begin_export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset,
-                                                   scale, eval_mode, task, largest_component, data_root, kept, allow_missing_gt))
 
 
 def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_size, ply_filename_out, offset=None,
@@ -287,6 +244,25 @@ def decode_two_pass(hand_branch, obj_branch, decoder, latent_vec, mano_results, 
     return {"vol_hand": vol_hand, "vol_obj": vol_obj, "voxel_size": new_voxel_size, "origin": new_origin.tolist(), "bbox": b}
 
 
+def write_hand_and_object(r, filename, hand_branch, obj_branch, offset=None, scale=None, eval_mode=False, task="obman", after_hand=None):
+    """<filename>_hand.ply, then <filename>_obj.ply, from the volumes of decode_two_pass.  As in the reference, the object mesh is
+    written with the hand mesh's ICP translation / scale as its offset / scale (utils/mesh.py:123-133,186-195); the caller's
+    `offset` / `scale` reach it only when the hand branch is off.  `after_hand(verts, faces, offset, scale, stats)` runs between the
+    two files when the hand has a surface.  Returns the per-surface (V, F) counts."""
+    stats = {}
+    if hand_branch:
+        v, f, offset, scale = convert_sdf_samples_to_ply(r["vol_hand"], r["origin"], r["voxel_size"], filename + "_hand.ply", None,
+                                                         None, eval_mode, task)
+        stats["hand"] = (0, 0) if v is None else (len(v), len(f))
+        if after_hand is not None and v is not None:
+            after_hand(v, f, offset, scale, stats)
+    if obj_branch:
+        v, f, _, _ = convert_sdf_samples_to_ply(r["vol_obj"], r["origin"], r["voxel_size"], filename + "_obj.ply", offset, scale,
+                                                False)
+        stats["obj"] = (0, 0) if v is None else (len(v), len(f))
+    return stats
+
+
 def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, latent_vec, mano_results, obj_results, cam_intr,
                                  specs, filename, N=256, max_batch=32 ** 3, offset=None, scale=None, device="cpu",
                                  label_out=False, viz=False, eval_mode=False, task="obman", grid_mode="reference", return_stats=False):
@@ -304,21 +280,15 @@ def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, l
     # (the volumes go to marching cubes only: a decoder set to the narrow-band fine sweep may use it)
     r = decode_two_pass(hand_branch, obj_branch, decoder, latent_vec, mano_results, obj_results, specs, N, grid_mode, cam_intr,
                         mc_only=True)
-    stats = {}
-    if hand_branch:
-        v, f, offset, scale = convert_sdf_samples_to_ply(r["vol_hand"], r["origin"], r["voxel_size"], filename + "_hand.ply", None,
-                                                         None, eval_mode, task)
-        stats["hand"] = (0, 0) if v is None else (len(v), len(f))
-        if label_out and v is not None:
-            vertices = np.array(v, copy=True)
-            for a in range(3):
-                vertices[:, a] = r["origin"][a] + vertices[:, a]
-            vertices = torch.from_numpy(vertices)
-            labels = label_points(decoder, latent_vec, mano_results, obj_results, specs, vertices)
-            write_label_outputs(vertices, f, labels, filename + "_hand", offset, scale, viz)
-            stats["labels"] = labels
-    if obj_branch:
-        v, f, _, _ = convert_sdf_samples_to_ply(r["vol_obj"], r["origin"], r["voxel_size"], filename + "_obj.ply", offset, scale,
-                                                False)
-        stats["obj"] = (0, 0) if v is None else (len(v), len(f))
+
+    def label_pass(v, f, offset, scale, stats):       # (between the two files: its launch stays ahead of the object's marching cubes)
+        vertices = np.array(v, copy=True)
+        for a in range(3):
+            vertices[:, a] = r["origin"][a] + vertices[:, a]
+        vertices = torch.from_numpy(vertices)
+        labels = label_points(decoder, latent_vec, mano_results, obj_results, specs, vertices)
+        write_label_outputs(vertices, f, labels, filename + "_hand", offset, scale, viz)
+        stats["labels"] = labels
+
+    stats = write_hand_and_object(r, filename, hand_branch, obj_branch, offset, scale, eval_mode, task, label_pass if label_out else None)
     return stats if return_stats else None

@@ -203,6 +203,57 @@ def test_eval_mode_icp_in_file_flow(tmp_path):
     assert np.abs(np.asarray(trans).reshape(3) - np.array([0.02, -0.01, 0.03])).max() < 5e-3
 
 
+def test_reconstruct_eval_mode_recovers_a_known_similarity(tmp_path):
+    """reconstruct(eval_mode=True) end to end: ground-truth prefetcher -> ICP enqueued in the midpoint hook -> finish -> the object
+    inherits the hand's transform.  The ground truth of every sample is its own plain hand file under a known similarity, so the
+    files of the eval-mode run are the plain run's files under the recorded (icp_trans, icp_scale), and those recover the similarity
+    within the bounds test_eval_mode_icp_in_file_flow uses for this ICP."""
+    import json
+    from alignsdf_amd.networks.model import build_decoder
+    from alignsdf_amd.ply import read_ply
+    from alignsdf_amd.reconstruct import reconstruct, synthetic_code_source
+    from alignsdf_amd.utils.mesh import ground_truth_mesh_path
+    specs = syn.specs_for("nerf3")
+    dec = build_decoder(specs, {k: torch.from_numpy(v) for k, v in syn.full_state_dict("nerf3").items()})
+    names = ["00000012", "00000047", "00000100"]
+    split = str(tmp_path / "split.json")
+    with open(split, "w") as fh:
+        json.dump({"filenames": ["data/obman/test/rgb/%s.jpg" % n for n in names]}, fh)
+    src = synthetic_code_source("nerf3")
+    shift = np.array([0.02, -0.01, 0.03])
+    plain_dir, eval_dir, data_root = str(tmp_path / "plain"), str(tmp_path / "eval"), str(tmp_path / "data")
+    plain = reconstruct(dec, specs, split, plain_dir, 0, 3, cube_dim=48, code_source=src)
+    truth = {}
+    for name in names:
+        pv, pf = read_ply(os.path.join(plain_dir, "meshes", name + "_hand.ply"))
+        truth[name] = pv.astype(np.float64) * 1.09 + shift
+        gt_path = ground_truth_mesh_path(os.path.join(eval_dir, "meshes", name + "_hand.ply"), "obman", data_root)
+        os.makedirs(os.path.dirname(gt_path), exist_ok=True)
+        with open(gt_path, "w") as fh:
+            for p in truth[name]:
+                fh.write("v %.9f %.9f %.9f\n" % tuple(p))
+            for t in pf:
+                fh.write("f %d %d %d\n" % tuple(t + 1))
+    recs = reconstruct(dec, specs, split, eval_dir, 0, 3, cube_dim=48, code_source=src, eval_mode=True, data_root=data_root)
+    assert [r["name"] for r in recs] == names and not any("icp_skipped" in r for r in recs)
+    for rec, before in zip(recs, plain):
+        assert (rec["V_hand"], rec["F_hand"], rec["V_obj"], rec["F_obj"]) == (before["V_hand"], before["F_hand"], before["V_obj"], before["F_obj"])
+        trans, scale = np.array(rec["icp_trans"]), rec["icp_scale"]
+        worst = {}
+        for part in ("hand", "obj"):
+            pv, pf = read_ply(os.path.join(plain_dir, "meshes", "%s_%s.ply" % (rec["name"], part)))
+            av, af = read_ply(os.path.join(eval_dir, "meshes", "%s_%s.ply" % (rec["name"], part)))
+            assert np.array_equal(af, pf)
+            worst[part] = np.abs(av - (pv.astype(np.float64) * scale + trans)).max()
+        av, _ = read_ply(os.path.join(eval_dir, "meshes", rec["name"] + "_hand.ply"))
+        found = (abs(scale - 1.09), np.abs(trans - shift).max(), np.abs(av - truth[rec["name"]]).max())
+        print("%s: files vs plain * icp_scale + icp_trans: hand %.3g obj %.3g; scale error %.3g, translation error %.3g, vertex error %.3g"
+              % ((rec["name"], worst["hand"], worst["obj"]) + found))
+        # two fp32 roundings of values below 2 (the plain file's and the aligned file's): under 5e-7
+        assert worst["hand"] <= 1e-6 and worst["obj"] <= 1e-6
+        assert found[0] < 5e-3 and found[1] < 5e-3 and found[2] < 2e-3
+
+
 def test_packed_weights_follow_parameter_updates():
     """The per-module cache of packed weights is refreshed after an in-place parameter update."""
     from alignsdf_amd.networks.model import build_decoder

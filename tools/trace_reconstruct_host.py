@@ -29,8 +29,6 @@ def timed(mod, name, label=None):
 
 
 timed(mu, "export_surface")
-timed(mu, "begin_export_surface")
-timed(mu, "end_export_surface")
 timed(mu, "write_ply")
 timed(mu, "place_vertices")
 timed(icp, "run_icp_f")
@@ -94,5 +92,5 @@ gaps = [ev[i][1].elapsed_time(ev[i + 1][0]) for i in range(len(ev) - 1)]
 print("K1 launches %d, mean %.1f ms; gaps after pass 1 (zoom readback): %s; gaps after pass 2 (next sample): %s" % (
     len(ev), sum(dur) / len(dur), ["%.1f" % g for g in gaps[0::2]], ["%.1f" % g for g in gaps[1::2]]))
 
-for name in ("begin_export_surface", "end_export_surface", "marching_cubes_device", "export_surface", "decode_grid", "set_sample", "event.synchronize", "tensor.cpu (bbox / MC sizes)"):
+for name in ("marching_cubes_device", "export_surface", "decode_grid", "set_sample", "event.synchronize", "tensor.cpu (bbox / MC sizes)"):
     print(name, ["%.0f+%.0f" % c for c in calls[name][-14:]])
