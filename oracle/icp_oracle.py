@@ -29,17 +29,47 @@ def solve_scale_trans(X, Y):
     return s, ym - s * xm
 
 
-def run_icp_f(points_source, points_target, max_iter=100, stop_error=1e-3, stop_improvement=1e-5):
-    """ICP_T_S.run_icp_f on already normalised source samples.  Returns (scale, trans[3], iterations, errors)."""
+def nearest_first_min(queries, refs, chunk_pairs=1 << 15):
+    """Exhaustive nearest neighbour with the brute-force kernel's arithmetic and tie rule: per pair d = d0*d0 + d1*d1 + d2*d2 in
+    that order in fp64 (the library is built with -ffp-contract=off: the same roundings), and argmin over the reference index,
+    so of several equal minima the FIRST - the lowest index - wins.  cKDTree returns the same distances but an arbitrary one of
+    tied neighbours.  Plain numpy, chunked over the queries (about `chunk_pairs` distances at a time: cache-sized, 30 000 x
+    30 000 in about three seconds).  Returns (d2 [nq], idx [nq])."""
+    q, r = np.asarray(queries, np.float64).reshape(-1, 3), np.asarray(refs, np.float64).reshape(-1, 3)
+    r0, r1, r2 = (np.ascontiguousarray(r[:, a])[None, :] for a in range(3))
+    d2, idx = np.empty(len(q)), np.empty(len(q), np.int64)
+    step = max(1, chunk_pairs // max(1, len(r)))
+    for lo in range(0, len(q), step):
+        c = q[lo:lo + step]
+        d = c[:, 0:1] - r0
+        d *= d
+        for col, ra in ((1, r1), (2, r2)):
+            t = c[:, col:col + 1] - ra
+            t *= t
+            d += t
+        k = d.argmin(1)
+        idx[lo:lo + step] = k
+        d2[lo:lo + step] = d[np.arange(len(c)), k]
+    return d2, idx
+
+
+def run_icp_f(points_source, points_target, max_iter=100, stop_error=1e-3, stop_improvement=1e-5, nearest=None):
+    """ICP_T_S.run_icp_f on already normalised source samples.  Returns (scale, trans[3], iterations, errors).
+    `nearest` (optional): a function (queries, refs) -> (squared distances, indices) that replaces the two KD-tree queries -
+    nearest_first_min where the choice among exactly tied neighbours matters."""
     ps, pt = np.asarray(points_source, np.float64), np.asarray(points_target, np.float64)
-    tree_t, tree_s = cKDTree(pt), cKDTree(ps)
+    if nearest is None:
+        tree_t, tree_s = cKDTree(pt), cKDTree(ps)
+        nn_t, nn_s = (lambda q: tree_t.query(q)[1]), (lambda q: tree_s.query(q)[1])
+    else:
+        nn_t, nn_s = (lambda q: nearest(q, pt)[1]), (lambda q: nearest(q, ps)[1])
     scale, trans = 1.0, np.zeros(3)
     previous, errors, it = 1e8, [], 0
     for it in range(max_iter):
         q_s = ps * scale + trans
-        idx_t = tree_t.query(q_s)[1]
+        idx_t = nn_t(q_s)
         ct = pt[idx_t]
-        idx_s = tree_s.query((pt - trans) / scale)[1]
+        idx_s = nn_s((pt - trans) / scale)
         cs = ps[idx_s] * scale + trans
         error = np.sqrt((((q_s - ct) ** 2).sum() + ((pt - cs) ** 2).sum()) / (len(ps) + len(pt)))
         errors.append(error)
@@ -52,10 +82,10 @@ def run_icp_f(points_source, points_target, max_iter=100, stop_error=1e-3, stop_
     return scale, trans, it + 1, errors
 
 
-def icp_trans_scale(points_source, points_target, vertices, max_iter=100):
+def icp_trans_scale(points_source, points_target, vertices, max_iter=100, nearest=None):
     """sample_mesh normalisation + run_icp_f + get_trans_scale + the vertex transform of export_source_mesh."""
     ps, n = normalise_source(points_source, points_target)
-    scale, trans, iters, errors = run_icp_f(ps, points_target, max_iter)
+    scale, trans, iters, errors = run_icp_f(ps, points_target, max_iter, nearest=nearest)
     all_scale = n["scale_target"] * scale / n["scale_source"]
     all_trans = trans + n["offset_target"] * scale - n["offset_source"] * n["scale_target"] * scale / n["scale_source"]
     v = (np.asarray(vertices, np.float64) - n["offset_source"]) / n["scale_source"] * n["scale_target"] + n["offset_target"]
