@@ -17,7 +17,8 @@ FEATURES_NERF = 1
 
 ERANGE = -6
 ENOSURF = -7
-ABI_VERSION = 130        # asdf_version() of the library these bindings were written for
+ENOGRAD = -8
+ABI_VERSION = 131        # asdf_version() of the library these bindings were written for
 
 # every symbol include/alignsdf_hip.h declares
 EXPORTS = (
@@ -31,7 +32,7 @@ EXPORTS = (
     "asdf_zoom_cube", "asdf_decode_grid_band_dev", "asdf_decode_grid_dev", "asdf_mc_emit_bounded",
     "asdf_sample_surface_workspace_bytes", "asdf_sample_surface", "asdf_icp_normalise",
     "asdf_decoder_set_sample_host", "asdf_decoder_set_cluster_timeout", "asdf_set_mfma_shape", "asdf_get_mfma_shape",
-    "asdf_debug_pack_host_f16w", "asdf_decoder_set_sample_pixel",
+    "asdf_debug_pack_host_f16w", "asdf_decoder_set_sample_pixel", "asdf_decode_points_grad",
 )
 MATH_F32, MATH_F16X3 = 0, 1
 MAX_CLASSES = 8
@@ -120,6 +121,7 @@ def lib():
     L.asdf_decode_grid_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]
     L.asdf_mc_emit_bounded.argtypes = [vp, i32, i32, i32, ctypes.c_double, vp, ctypes.c_size_t, vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp]
     L.asdf_decode_points.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.asdf_decode_points_grad.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     L.asdf_decoder_set_classifier.argtypes = [vp, vp, vp, i32]
     L.asdf_decode_points_cls.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     L.asdf_neg_bbox.argtypes = [vp, i32, i32, i32, vp, vp]

@@ -499,7 +499,7 @@ static int decode_grid_band_impl(asdf_decoder_t* d, int32_t N, const float* orig
 
 extern "C" {
 
-int asdf_version(void) { return 130; }
+int asdf_version(void) { return 131; }
 
 int asdf_set_mfma_shape(int shape) {
   if (shape != 0 && shape != 16 && shape != 32) return ASDF_EINVAL;
@@ -517,6 +517,7 @@ const char* asdf_strerror(int code) {
     case ASDF_ENOSPC: return "buffer or workspace too small";
     case ASDF_ERANGE: return "Surface level must be within volume data range.";
     case ASDF_ENOSURF: return "No surface found at the given iso value.";
+    case ASDF_ENOGRAD: return "the gradient kernel does not cover this decoder (SeparateDecoder with affine point features only)";
     default: return "unknown error";
   }
 }
@@ -630,6 +631,7 @@ int asdf_decoder_create(const asdf_decoder_spec_t* spec, const asdf_head_params_
   if (e == hipSuccess) e = k1_prepare();
   if (e == hipSuccess) e = k1_cls_prepare();
   if (e == hipSuccess) e = k1pa_prepare();
+  if (e == hipSuccess) e = k1g_prepare();
   if (e == hipSuccess) e = hipMalloc((void**)&d->latent_stage, kLatent * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&d->status, ASDF_STATUS_WORDS * sizeof(int));
   if (e == hipSuccess) e = hipMemset(d->status, 0, ASDF_STATUS_WORDS * sizeof(int));
@@ -940,6 +942,30 @@ int asdf_decode_points(asdf_decoder_t* d, const float* xyz_dev, int64_t M, float
   std::memset(&p, 0, sizeof(p));
   p.sdf0 = sdf_hand_dev; p.sdf1 = sdf_obj_dev; p.xyz = xyz_dev; p.P = M; p.N = 1; p.mode = kPointList;
   return launch_decode(d, p, (hipStream_t)stream);
+}
+
+int asdf_decode_points_grad(asdf_decoder_t* d, const float* xyz_dev, int64_t M, float* sdf_hand_dev, float* grad_hand_dev,
+                            float* sdf_obj_dev, float* grad_obj_dev, void* stream) {
+  if (!d || M < 0 || (M > 0 && !xyz_dev)) return ASDF_EINVAL;
+  if (!d->sample_bound) return ASDF_EINVAL;
+  // SeparateDecoder with affine point features and an ordinary (per-sample constant) latent
+  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound) return ASDF_ENOGRAD;
+  const bool want0 = sdf_hand_dev || grad_hand_dev, want1 = sdf_obj_dev || grad_obj_dev;
+  if (M == 0 || (!want0 && !want1)) return ASDF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // always the fp32 chain's weights and constants: d->math and the MFMA shape of the split-half sweeps are not looked at
+  DecodeParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.stream = d->stream; p.cst = d->cst;
+  p.sdf0 = sdf_hand_dev; p.sdf1 = sdf_obj_dev; p.xyz = xyz_dev; p.P = M; p.N = 1; p.mode = kPointList;
+  p.first_mlp = want0 ? 0 : 1;
+  p.num_mlps = want0 && want1 ? 2 : 1;
+  p.pf = d->spec.point_feats[0];
+  GradParams g;
+  g.grad0 = grad_hand_dev; g.grad1 = grad_obj_dev;
+  k1g_launch(p, g, k1g_grid(M, d->num_cus), st);
+  ASDF_HIP(hipGetLastError());
+  return ASDF_OK;
 }
 
 int asdf_decoder_set_math(asdf_decoder_t* d, int32_t math) {

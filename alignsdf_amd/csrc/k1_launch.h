@@ -40,6 +40,14 @@ void k1_cls_launch(int kp, bool two_out, const DecodeParams& p, int grid, hipStr
 // the fp32 chain with a pixel-aligned latent (k1pa_kernels.hip): SeparateDecoder, xyz features, lattice sweeps and point lists
 hipError_t k1pa_prepare();
 void k1pa_launch(const DecodeParams& p, const PixelParams& px, int grid, hipStream_t st);
+// the fp32 chain in forward mode over a point list (k1g_kernels.hip): sdf and d sdf / d xyz; SeparateDecoder, affine point features
+struct GradParams {
+  float* grad0;         // [P][3] d sdf_hand / d xyz (may be null)
+  float* grad1;         // [P][3] d sdf_obj / d xyz (may be null)
+};
+hipError_t k1g_prepare();
+int k1g_grid(long long points, int num_cus);      // workgroups of a launch over `points` points (32 per workgroup tile)
+void k1g_launch(const DecodeParams& p, const GradParams& g, int grid, hipStream_t st);
 void k1h_launch(int kp, bool two_out, const DecodeParams& p, int grid, hipStream_t st);
 // the W form (16x16x32 MFMAs) of the SeparateDecoder kernels with affine point features: k1hw_kernels.hip
 hipError_t k1hw_prepare();

@@ -193,6 +193,19 @@ def pixel_align_refusal(combined, point_feat_size, encode_style, num_class):
     return None
 
 
+def grad_refusal(combined, point_feat_size, encode_style, pixel_align):
+    """Why (a string) the gradient form of the fp32 chain (HipSdfDecoder.decode_points_grad, csrc/k1g_kernels.hip) does not cover a
+    decoder of this shape, or None.  It is built for SeparateDecoder with point features that are affine in xyz: plain xyz and the
+    "hand" / "obj" / "both" kinematic embeddings - every shipped config.  A part classifier does not matter (it is not evaluated)."""
+    if combined:
+        return "CombinedDecoder (the gradient kernel is built for SeparateDecoder)"
+    if pixel_align:
+        return "pixel-aligned latent (the bicubic gather is not differentiated)"
+    if encode_style == "nerf" and int(point_feat_size) > 3:
+        return "NeRF encoding with PointFeatSize %d (only point features affine in xyz are built)" % int(point_feat_size)
+    return None
+
+
 class HipSdfDecoder:
     """Device-resident packed decoder.  One instance per (module, device)."""
 
@@ -1285,6 +1298,30 @@ class HipSdfDecoder:
             _native.check(self._L.asdf_decode_points(self._h, xyz.data_ptr(), M, hand.data_ptr(), obj.data_ptr(),
                                                      self._stream()), "asdf_decode_points")
         return hand, obj
+
+    def grad_refusal(self):
+        """grad_refusal() of this decoder: why decode_points_grad would refuse, or None."""
+        return grad_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
+
+    def decode_points_grad(self, xyz, hand=True, obj=True):
+        """SDF and its gradient with respect to the normalised query points [M,3], in one forward-mode pass of the fp32 chain
+        (csrc/k1g_kernels.hip; the math mode of the sweeps is neither read nor changed).  Returns (sdf_hand [M], grad_hand [M,3],
+        sdf_obj [M], grad_obj [M,3]) device tensors, None for a head switched off.  The SDF values are decode_points' under
+        set_math("f32"), bit for bit.  NotImplementedError(reason) for a decoder grad_refusal() does not cover."""
+        why = self.grad_refusal()
+        if why is not None:
+            raise NotImplementedError("the gradient kernel does not cover this decoder: %s" % why)
+        xyz = xyz.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        M = xyz.shape[0]
+        new = lambda on, *shape: torch.empty(shape, dtype=torch.float32, device=self.device) if on else None
+        sh, gh, so, go = new(hand, M), new(hand, M, 3), new(obj, M), new(obj, M, 3)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            code = self._L.asdf_decode_points_grad(self._h, xyz.data_ptr(), M, ptr(sh), ptr(gh), ptr(so), ptr(go), self._stream())
+        if code == _native.ENOGRAD:        # (the library's own gate: whatever grad_refusal() missed is still a refusal, not a native error)
+            raise NotImplementedError("the gradient kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
+        _native.check(code, "asdf_decode_points_grad")
+        return sh, gh, so, go
 
     def classify_points(self, xyz, want_sdf=True):
         """decode_points plus the part classifier: (hand [M], obj [M], scores [M, num_class], labels [M] int64) - the

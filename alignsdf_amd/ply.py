@@ -4,11 +4,19 @@ deep_sdf/mesh.py:107-112)."""
 import numpy as np
 
 
-def write_ply(path, verts, faces):
+def write_ply(path, verts, faces, normals=None):
+    """normals [V, 3] (optional): written as `property float nx / ny / nz` behind z; without them the file is the layout above."""
     verts = np.ascontiguousarray(verts, dtype="<f4").reshape(-1, 3)
     faces = np.ascontiguousarray(faces, dtype="<i4").reshape(-1, 3)
-    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
-              "property float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(verts), len(faces)))
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype="<f4").reshape(-1, 3)
+        if len(normals) != len(verts):
+            raise ValueError("%d normals for %d vertices" % (len(normals), len(verts)))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+        verts = np.ascontiguousarray(np.hstack([verts, normals]))
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%selement face %d\nproperty list uchar int vertex_indices\n"
+              "end_header\n" % (len(verts), props, len(faces)))
     rec = np.empty(len(faces), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     rec["n"] = 3
     rec["idx"] = faces
@@ -18,20 +26,39 @@ def write_ply(path, verts, faces):
         f.write(rec.tobytes())
 
 
-def read_ply(path):
-    """Inverse of write_ply (for tests)."""
+_PLY_SCALARS = {"char": "i1", "uchar": "u1", "short": "<i2", "ushort": "<u2", "int": "<i4", "uint": "<u4", "float": "<f4", "double": "<f8",
+                "int8": "i1", "uint8": "u1", "int16": "<i2", "uint16": "<u2", "int32": "<i4", "uint32": "<u4", "float32": "<f4",
+                "float64": "<f8"}
+
+
+def read_ply(path, with_normals=False):
+    """Inverse of write_ply: (verts, faces), or (verts, faces, normals or None) with with_normals=True.  The vertex record is
+    taken from the header's scalar properties, so files with normals (or other per-vertex scalars) read correctly."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
     nv = nf = 0
+    element, fields = None, []
     for line in data[:end].decode("ascii").splitlines():
-        if line.startswith("element vertex"):
-            nv = int(line.split()[-1])
-        if line.startswith("element face"):
-            nf = int(line.split()[-1])
-    verts = np.frombuffer(data, dtype="<f4", count=nv * 3, offset=end).reshape(nv, 3)
-    rec = np.frombuffer(data, dtype=[("n", "u1"), ("idx", "<i4", (3,))], count=nf, offset=end + nv * 12)
-    return verts.copy(), rec["idx"].copy()
+        word = line.split()
+        if line.startswith("element"):
+            element = word[1]
+            if element == "vertex":
+                nv = int(word[-1])
+            if element == "face":
+                nf = int(word[-1])
+        elif line.startswith("property") and element == "vertex":
+            if word[1] == "list":
+                raise ValueError("list property %r on the vertex element" % word[-1])
+            fields.append((word[2], _PLY_SCALARS[word[1]]))
+    vrec = np.frombuffer(data, dtype=np.dtype(fields), count=nv, offset=end)
+    verts = np.stack([vrec[k] for k in ("x", "y", "z")], 1).astype(np.float32)
+    rec = np.frombuffer(data, dtype=[("n", "u1"), ("idx", "<i4", (3,))], count=nf, offset=end + nv * vrec.dtype.itemsize)
+    if not with_normals:
+        return verts, rec["idx"].copy()
+    names = vrec.dtype.names
+    normals = np.stack([vrec[k] for k in ("nx", "ny", "nz")], 1).astype(np.float32) if all(k in names for k in ("nx", "ny", "nz")) else None
+    return verts, rec["idx"].copy(), normals
 
 
 def write_ply_ascii(path, verts, faces=None, vertex_colors=None):

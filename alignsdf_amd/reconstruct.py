@@ -57,12 +57,15 @@ def reconstruct_sample(decoder, specs, latent, mano_results, obj_results, N, mes
 
 def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, end_point, task="obman", device="cuda", scale=None,
                 cube_dim=128, label_out=False, viz=False, eval_mode=False, code_source=None, grid_mode="reference",
-                data_root="data", allow_missing_gt=False, fast=None, stride=1, on_record=None):
+                data_root="data", allow_missing_gt=False, fast=None, stride=1, on_record=None, normals=False):
     """Reconstruct samples [start_point, end_point) of a split file (reconstruct.py:33-95).  `loaded_model` is the
     decoder module, or any wrapper exposing it as `.module.decoder` / `.decoder` like the reference's DataParallel model.
     `fast`: see pipelined_two_pass (default: ordinary sweeps, every voxel at <= 1e-5).  `stride` > 1: every stride-th sample of the
     range (the strided shards of dist_reconstruct --shard strided).  `on_record(rec)` is called with every finished sample's record
-    (dist_reconstruct keeps its shard's records file current with it).  Returns the list of per-sample records."""
+    (dist_reconstruct keeps its shard's records file current with it).  `normals=True`: every file carries per-vertex unit normals
+    (nx / ny / nz: the normalised analytic SDF gradient, see pipelined_two_pass) and every record `normals_degenerate_hand` / `_obj`;
+    a decoder the gradient kernel does not cover raises NotImplementedError before the first sweep and before any file is written.
+    Returns the list of per-sample records."""
     stride = max(1, int(stride))
     with open(split_filename, "r") as f:
         names = json.load(f)["filenames"][int(start_point):int(end_point):stride]
@@ -75,7 +78,7 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
         raise ValueError("reconstruct() needs a code_source: npz_code_source(<dir of per-sample .npz codes>), "
                          "model_output_code_source(<encoder callable>), or synthetic_code_source(...) for tests and benchmarks")
     out = SampleWriter(output_dir, (start_point, end_point, stride), cube_dim, specs.get("HandBranch", True), scale, viz,
-                       (task, data_root, allow_missing_gt) if eval_mode else None)
+                       (task, data_root, allow_missing_gt) if eval_mode else None, normals=normals)
 
     def samples():
         for k, path in enumerate(names):
@@ -83,10 +86,11 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
             out.prefetch(name)
             yield ((index, name), *code_source(name, index))
 
+    extra = {"normals": True} if normals else {}          # (the option travels only when it is on)
     try:
         with torch.no_grad():
             for (index, name), r in pipelined_two_pass(decoder, specs, samples(), cube_dim, grid_mode, host_copy=True,
-                                                        label_out=label_out and out.hand_on, report=out.sweeps, fast=fast,
+                                                        label_out=label_out and out.hand_on, report=out.sweeps, fast=fast, **extra,
                                                         midpoint=out.begin_hand if out.gt is not None else None):
                 rec = out.write(index, name, r)
                 if on_record is not None:
@@ -127,6 +131,12 @@ def add_sweep_arguments(p):
                         "corners of every cell that can be active re-evaluated as an ordinary sweep would)")
 
 
+def add_normals_argument(p):
+    p.add_argument("--normals", action="store_true",
+                   help="write per-vertex unit normals (property float nx / ny / nz) into every mesh file: the analytic gradient of the "
+                        "SDF at the vertex, normalised - one forward-mode pass of the decoder per surface.  Default: x y z only")
+
+
 def apply_sweep_arguments(args):
     if args.coarse:
         os.environ["ASDF_COARSE"] = args.coarse          # read when the decoder is packed
@@ -149,6 +159,7 @@ def main(argv=None):
     p.add_argument("--allow_missing_gt", action="store_true", help="eval mode: write unaligned meshes when a ground-truth mesh is missing instead of aborting")
     p.add_argument("--cube_dim", type=int, default=128, help="grid resolution (reference CLI hard-codes 128, reconstruct.py:178)")
     add_sweep_arguments(p)
+    add_normals_argument(p)
     args = p.parse_args(argv)
     apply_sweep_arguments(args)
     split = args.split_filename or {"obman": "input/obman.json", "dexycb": "input/dexycb.json"}[args.task]
@@ -161,7 +172,7 @@ def main(argv=None):
     source = code_source_from_args(args, specs, p)
     return reconstruct(decoder, specs, split, output_dir, args.start_point, args.end_point, task=args.task, cube_dim=args.cube_dim,
                        label_out=args.label_out, viz=args.viz, eval_mode=args.eval_mode, code_source=source,
-                       allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None)
+                       allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None, normals=args.normals)
 
 
 if __name__ == "__main__":

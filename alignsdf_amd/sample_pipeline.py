@@ -10,7 +10,7 @@ from .utils import mesh as mesh_utils, utils
 
 
 def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_copy=False, label_out=False, midpoint=None, report=None,
-                       fast=None):
+                       fast=None, normals=False):
     """Software pipeline over independent samples.  `samples` yields (key, latent, mano_results, obj_results); the
     generator yields (key, result) in order, where result holds the pass-2 volumes (device), the zoom cube and the
     marching-cubes output per enabled branch (`verts_*`, `faces_*` device tensors, absent when MC found no surface).
@@ -40,8 +40,13 @@ def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_c
     k+2: GPU work it enqueues (the eval-mode ICP of sample k's hand mesh) lands between two decoder passes instead of
     behind both, and its host part is covered by the pass that is already running.
 
+    normals=True (with host_copy) runs the normal pass behind K8: the analytic SDF gradient of the surface's own head at every kept
+    vertex (decode_points_grad at origin + v * voxel_size), normalised, (0, 0, 0) where it has no direction - `kept_normals_*` on the
+    device, `host_kept_normals_*` at input capacity with the other copies.  The sample is re-bound first, as for the label pass.  A
+    decoder the gradient kernel does not cover raises NotImplementedError before the first sweep.
+
     report, if given (a dict), receives the evaluator that ran and a snapshot of its sweep counters (see write_sweeps_json)."""
-    yield from SamplePipeline(decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast).run()
+    yield from SamplePipeline(decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals).run()
 
 
 @dataclasses.dataclass(slots=True, eq=False)
@@ -59,14 +64,17 @@ class InFlight:
 class SamplePipeline:
     """pipelined_two_pass: the decoder and the state its stages share, one method per stage, and the window over the samples (run)."""
 
-    def __init__(self, decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast):
+    def __init__(self, decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals=False):
         self.specs, self.N, self.host_copy, self.label_out, self.midpoint = specs, N, host_copy, label_out, midpoint
+        self.normals = bool(normals)
         self.samples = (InFlight(key, codes) for key, *codes in samples)   # (lazy: a sample is fetched when the window asks for it)
         self.head = next(self.samples, None)
         if self.head is None:                      # (an empty stream: no decoder is asked for)
             return
         # the HIP kernels, or the module on PyTorch-ROCm for variants they do not cover
         self.hip = hip = utils.decoder_for(decoder, specs, self.head.codes[1])
+        if self.normals:
+            mesh_utils.require_normals(hip)        # (before the first sweep: no run of files without the normals that were asked for)
         if fast is not None and hasattr(hip, "set_fast"):
             hip.set_fast(bool(fast))
         if report is not None:                     # (the caller's `sweeps.json`: which evaluator ran, and its counters at the start)
@@ -178,7 +186,7 @@ class SamplePipeline:
         return done
 
     def post_process(self, s):
-        """Label pass, component filter and host copies of the surfaces marching cubes found."""
+        """Label pass, component filter, normal pass and host copies of the surfaces marching cubes found."""
         r = s.result
         for _, part in self.parts:
             if "verts_" + part not in r:
@@ -196,6 +204,14 @@ class SamplePipeline:
                 kv, kf, counts = keep_largest_component_device(v, f, r["voxel_size"], r["origin"])
                 r["kept_dev_" + part] = (kv, kf, counts)       # (the eval-mode hook samples the kept surface on the device)
                 copies = {"kept_verts_": kv, "kept_faces_": kf, "kept_counts_": counts}
+                if self.normals:
+                    # the normal pass, on the kept vertices (rows past the kept count hold no vertex: whatever comes out of them is
+                    # never read) - the decoder holds the next sample's constants by now
+                    if self.bound is not s:
+                        self.bind(s)
+                    res = self.hip.decode_points_grad(mesh_utils.lattice_points(kv, r["origin"], r["voxel_size"]), hand=part == "hand",
+                                                      obj=part == "obj")
+                    r["kept_normals_" + part] = copies["kept_normals_"] = mesh_utils.unit_normals(res[1] if part == "hand" else res[3])
                 if "labels_" + part in r:
                     copies.update({"verts_": v, "faces_": f, "labels_": r["labels_" + part]})
                 for name, t in copies.items():

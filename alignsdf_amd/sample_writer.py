@@ -41,11 +41,11 @@ class FileWriter:
         if first is not None:
             raise first
 
-    def write_ply(self, path, verts, faces):
+    def write_ply(self, path, verts, faces, normals=None):
         from .ply import write_ply
         self.poll()
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        self.jobs.append((path, self.pool.submit(write_ply, path, verts, faces)))
+        self.jobs.append((path, self.pool.submit(write_ply, path, verts, faces, normals)))
 
     def close(self, failing=False):
         from .frontend import restore_gil_handover
@@ -70,10 +70,11 @@ class SampleWriter:
     its ground truth in eval mode, the object under the hand's transform), the label files follow, and a record says what was written.
     close() ends the helpers and leaves the shard's sweeps report next to meshes/."""
 
-    def __init__(self, output_dir, shard, cube_dim, hand_on, scale=None, viz=False, ground_truth=None):
+    def __init__(self, output_dir, shard, cube_dim, hand_on, scale=None, viz=False, ground_truth=None, normals=False):
         """`shard` = (start_point, end_point, stride), for the sweeps report; `ground_truth` = (task, data_root, allow_missing_gt) in
-        eval mode - the hand is what gets aligned, so without a hand branch there is no prefetcher."""
-        self.output_dir, self.shard, self.cube_dim = output_dir, shard, cube_dim
+        eval mode - the hand is what gets aligned, so without a hand branch there is no prefetcher.  `normals`: the results carry
+        `host_kept_normals_*` (pipelined_two_pass(normals=True)) and every file is written with them."""
+        self.output_dir, self.shard, self.cube_dim, self.normals = output_dir, shard, cube_dim, bool(normals)
         self.mesh_dir = os.path.join(output_dir, "meshes")
         os.makedirs(self.mesh_dir, exist_ok=True)
         self.hand_on, self.scale, self.viz = hand_on, scale, viz
@@ -121,7 +122,13 @@ class SampleWriter:
             if job is None:
                 rec["icp_skipped"] = True          # allow_missing_gt: no ground-truth mesh, written unaligned
         points, trans, icp_scale = mesh_utils.apply_icp(job, points)
-        self.writer.write_ply(base + ".ply", points, faces)
+        if self.normals:
+            # (unit normals of the kept vertices: the ICP's translation and positive scale leave them as they are)
+            normals = r["host_kept_normals_" + part][:len(points)].numpy()
+            rec["normals_degenerate_" + part] = mesh_utils.count_degenerate(normals)
+            self.writer.write_ply(base + ".ply", points, faces, normals)
+        else:
+            self.writer.write_ply(base + ".ply", points, faces)
         return trans, icp_scale
 
     def write_labels(self, base, r, rec, offset, scale):

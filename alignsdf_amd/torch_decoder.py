@@ -257,6 +257,36 @@ class TorchModuleDecoder:
         h, o, _ = self._decode(xyz.detach().to(self.device, torch.float32).contiguous())
         return h, o
 
+    def decode_points_grad(self, xyz, hand=True, obj=True):
+        """The interface of HipSdfDecoder.decode_points_grad by torch autograd through the module's own forward (one backward per
+        head and chunk): (sdf_hand [M], grad_hand [M,3], sdf_obj [M], grad_obj [M,3]), None for a head switched off or absent."""
+        if self._sample is None:
+            raise ValueError("no sample bound: call set_sample first")
+        xyz = xyz.detach().to(self.device, torch.float32).contiguous()
+        M = xyz.shape[0]
+        new = lambda on, *shape: torch.empty(shape, dtype=torch.float32, device=self.device) if on else None
+        out = [new(hand, M), new(hand, M, 3), new(obj, M), new(obj, M, 3)]
+        module = self.module
+        was_training = module.training
+        module.eval()
+        try:
+            with torch.enable_grad():
+                for head in range(0, M, CHUNK):
+                    x = xyz[head:head + CHUNK].clone().requires_grad_()
+                    values = self._decode_chunk(module, x)[:2]
+                    for k, (on, v) in enumerate(zip((hand, obj), values)):
+                        if not on:
+                            continue
+                        if v is None:
+                            out[2 * k] = out[2 * k + 1] = None
+                            continue
+                        g, = torch.autograd.grad(v.sum(), x, retain_graph=True)
+                        out[2 * k][head:head + CHUNK] = v.detach().reshape(-1)
+                        out[2 * k + 1][head:head + CHUNK] = g
+        finally:
+            module.train(was_training)
+        return tuple(out)
+
     def classify_points(self, xyz, want_sdf=True):
         if not self.num_class:
             raise ValueError("this decoder has no classifier_head (specs['ClassifierBranch'] is off)")

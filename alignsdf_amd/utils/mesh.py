@@ -105,15 +105,94 @@ def apply_icp(job, points):
     return r["vertices"], np.asarray(r["all_trans"]).reshape(1, 3), np.asarray(r["all_scale"]).reshape(1)
 
 
+def normals_refusal(evaluator):
+    """Why (a string) this evaluator cannot give SDF gradients, or None: the native gradient kernel covers SeparateDecoder with point
+    features affine in xyz (hip_decoder.grad_refusal); the module path differentiates whatever it evaluates."""
+    refusal = getattr(evaluator, "grad_refusal", None)
+    return refusal() if callable(refusal) else None
+
+
+def require_normals(evaluator):
+    """Raise before anything is swept or written when `evaluator` cannot give the gradients vertex normals are made of."""
+    why = normals_refusal(evaluator)
+    if why is not None:
+        raise NotImplementedError("vertex normals need the SDF gradient, which the native kernel does not cover here: %s" % why)
+
+
+def unit_normals(grad):
+    """grad [V, 3] (device) -> grad / |grad|, (0, 0, 0) where the gradient has zero length or is not finite.  The SDF is negative
+    inside, so the normals point out of the shape."""
+    length = torch.linalg.vector_norm(grad, dim=1, keepdim=True)
+    ok = torch.isfinite(length) & (length > 0)
+    return torch.where(ok, grad / torch.where(ok, length, torch.ones_like(length)), torch.zeros_like(grad))
+
+
+def lattice_points(verts_d, voxel_grid_origin, voxel_size):
+    """Marching-cubes vertices (lattice units, device) -> their normalised fp32 positions origin + v * voxel_size, on the device (the
+    vertex arithmetic of utils/mesh.py:138-141): where the normal pass evaluates the decoder.  Spacing and origin travel as launch
+    arguments - no host-to-device copy, so nothing here waits for the stream."""
+    pts = verts_d * float(voxel_size)
+    for a in range(3):
+        pts[:, a] += float(voxel_grid_origin[a])
+    return pts
+
+
+def count_degenerate(normals):
+    """Number of (0, 0, 0) rows of a host array of unit normals."""
+    return int((~np.asarray(normals).any(axis=1)).sum())
+
+
+class VertexNormals:
+    """points [V, 3] (normalised coordinates, device) -> unit normals [V, 3] of one surface: grad / |grad| of the surface's own head
+    of the BOUND evaluator (HipSdfDecoder / TorchModuleDecoder.decode_points_grad).  `degenerate` is the number of (0, 0, 0) normals of
+    the last call."""
+
+    def __init__(self, evaluator, part):
+        require_normals(evaluator)
+        self.evaluator, self.part, self.degenerate = evaluator, part, 0
+
+    def __call__(self, points):
+        res = self.evaluator.decode_points_grad(points, hand=self.part == "hand", obj=self.part == "obj")
+        grad = res[1] if self.part == "hand" else res[3]
+        if grad is None:
+            raise ValueError("the evaluator has no %s head to take normals from" % self.part)
+        n = unit_normals(grad)
+        self.degenerate = int((~n.any(dim=1)).sum().item())
+        return n
+
+
+def _normals_callable(normals, ply_filename_out, part=None):
+    """The `normals` option of export_surface: a callable as it is; an evaluator with decode_points_grad -> VertexNormals of head
+    `part` ("hand" / "obj"; None: the head the file name ends in, <name>_hand.ply / <name>_obj.ply, as ground_truth_mesh_path reads
+    it)."""
+    if not normals:
+        return None
+    if hasattr(normals, "decode_points_grad"):
+        part = part or str(ply_filename_out).split("_")[-1].split(".")[0]
+        if part not in ("hand", "obj"):
+            raise ValueError("normals from an evaluator need normals_part=\"hand\" / \"obj\" or a file name that ends in _hand.ply / "
+                             "_obj.ply (got %r)" % (ply_filename_out,))
+        return VertexNormals(normals, part)
+    if not callable(normals):
+        raise TypeError("normals: a bound evaluator (decode_points_grad) or a callable points -> unit normals")
+    return normals
+
+
 def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, eval_mode=False,
-                   task="obman", largest_component=True, data_root="data", kept=None, allow_missing_gt=False):
+                   task="obman", largest_component=True, data_root="data", kept=None, allow_missing_gt=False, normals=False,
+                   normals_part=None):
     """The host tail of convert_sdf_samples_to_ply for an already extracted surface (utils/mesh.py:360-397): place_vertices, the
     largest-component filter, in eval mode the translate+scale ICP (K7) against the ground-truth mesh, export.
     Returns (verts, faces, trans, scale).  `kept` = (verts, faces) of the largest component in lattice units when the caller has
     already run the device filter; otherwise the surface is filtered here on the device (K8; host arrays are uploaded for it -
     there is no host implementation in the product).  A missing ground-truth file aborts like the reference (its trimesh.load
     raises at utils/mesh.py:389) - a wrong data_root must not produce a full run of silently unaligned meshes; with
-    allow_missing_gt the mesh is written unaligned."""
+    allow_missing_gt the mesh is written unaligned.
+    `normals`: the bound evaluator, or a callable that maps normalised points (device, [V, 3]) to unit normals - the file then carries
+    nx / ny / nz per vertex, evaluated at origin + v * voxel_size of the written vertices (before offset, scale and ICP: a
+    translation and a positive uniform scale leave a normal as it is).  An evaluator gives the normals of head `normals_part`
+    ("hand" / "obj"; by default the one the file name ends in)."""
+    normals = _normals_callable(normals, ply_filename_out, normals_part)
     if kept is None and largest_component:
         vd = verts_d if isinstance(verts_d, torch.Tensor) else torch.as_tensor(np.asarray(verts_d))
         fd = faces_d if isinstance(faces_d, torch.Tensor) else torch.as_tensor(np.asarray(faces_d))
@@ -138,20 +217,25 @@ def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename
                                     "unaligned meshes instead" % (gt_path, data_root))
     out_v, trans, sc = apply_icp(job, out_v)
     if ply_filename_out:
+        out_n = None
+        if normals is not None:
+            written = kept[0] if kept is not None else verts_d
+            written = written if isinstance(written, torch.Tensor) else torch.as_tensor(np.asarray(written))
+            out_n = normals(lattice_points(written.cuda().float(), voxel_grid_origin, voxel_size)).cpu().numpy()
         os.makedirs(os.path.dirname(os.path.abspath(ply_filename_out)), exist_ok=True)
-        write_ply(ply_filename_out, out_v, out_f)
+        write_ply(ply_filename_out, out_v, out_f, out_n)
     return verts, faces, trans, sc
 
 
 def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_size, ply_filename_out, offset=None,
                                scale=None, eval_mode=False, task="obman", largest_component=True, data_root="data",
-                               allow_missing_gt=False):
+                               allow_missing_gt=False, normals=False, normals_part=None):
     """Iso-surface of one SDF volume -> .ply (utils/mesh.py:331-399).  Returns (verts, faces, trans, scale) with
     verts / faces the raw marching-cubes output like the reference.  MC failures are logged and skipped exactly
     like the reference (utils/mesh.py:353-358).  The written file holds the largest watertight component when the
     surface splits into several (utils/mesh.py:371-381, K8 / alignsdf_amd.mesh_post); in eval mode it is first aligned to
     the ground-truth mesh by the translate+scale ICP (utils/mesh.py:385-395, alignsdf_amd.icp) and `trans`, `scale`
-    are the ICP's; otherwise they are zeros / one."""
+    are the ICP's; otherwise they are zeros / one.  `normals`, `normals_part`: see export_surface."""
     vol = pytorch_3d_sdf_tensor if isinstance(pytorch_3d_sdf_tensor, torch.Tensor) else torch.as_tensor(np.asarray(pytorch_3d_sdf_tensor))
     if not vol.is_cuda:
         vol = vol.cuda()
@@ -162,7 +246,7 @@ def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_s
         print(e)
         return None, None, np.array([0, 0, 0]), np.array([1])
     return export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset, scale, eval_mode, task,
-                          largest_component, data_root, allow_missing_gt=allow_missing_gt)
+                          largest_component, data_root, allow_missing_gt=allow_missing_gt, normals=normals, normals_part=normals_part)
 
 
 # colour per part label of the `--viz` output (the table of utils/mesh.py:305-310)
@@ -244,28 +328,36 @@ def decode_two_pass(hand_branch, obj_branch, decoder, latent_vec, mano_results, 
     return {"vol_hand": vol_hand, "vol_obj": vol_obj, "voxel_size": new_voxel_size, "origin": new_origin.tolist(), "bbox": b}
 
 
-def write_hand_and_object(r, filename, hand_branch, obj_branch, offset=None, scale=None, eval_mode=False, task="obman", after_hand=None):
+def write_hand_and_object(r, filename, hand_branch, obj_branch, offset=None, scale=None, eval_mode=False, task="obman", after_hand=None,
+                          normals=None):
     """<filename>_hand.ply, then <filename>_obj.ply, from the volumes of decode_two_pass.  As in the reference, the object mesh is
     written with the hand mesh's ICP translation / scale as its offset / scale (utils/mesh.py:123-133,186-195); the caller's
     `offset` / `scale` reach it only when the hand branch is off.  `after_hand(verts, faces, offset, scale, stats)` runs between the
-    two files when the hand has a surface.  Returns the per-surface (V, F) counts."""
+    two files when the hand has a surface.  `normals`: the evaluator, still bound to this sample - the files then carry vertex normals
+    and the stats their `normals_degenerate_<part>` counts.  Returns the per-surface (V, F) counts."""
     stats = {}
+    fn = {part: VertexNormals(normals, part) if normals is not None else False for part in ("hand", "obj")}
     if hand_branch:
         v, f, offset, scale = convert_sdf_samples_to_ply(r["vol_hand"], r["origin"], r["voxel_size"], filename + "_hand.ply", None,
-                                                         None, eval_mode, task)
+                                                         None, eval_mode, task, normals=fn["hand"])
         stats["hand"] = (0, 0) if v is None else (len(v), len(f))
+        if normals is not None and v is not None:
+            stats["normals_degenerate_hand"] = fn["hand"].degenerate
         if after_hand is not None and v is not None:
             after_hand(v, f, offset, scale, stats)
     if obj_branch:
         v, f, _, _ = convert_sdf_samples_to_ply(r["vol_obj"], r["origin"], r["voxel_size"], filename + "_obj.ply", offset, scale,
-                                                False)
+                                                False, normals=fn["obj"])
         stats["obj"] = (0, 0) if v is None else (len(v), len(f))
+        if normals is not None and v is not None:
+            stats["normals_degenerate_obj"] = fn["obj"].degenerate
     return stats
 
 
 def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, latent_vec, mano_results, obj_results, cam_intr,
                                  specs, filename, N=256, max_batch=32 ** 3, offset=None, scale=None, device="cpu",
-                                 label_out=False, viz=False, eval_mode=False, task="obman", grid_mode="reference", return_stats=False):
+                                 label_out=False, viz=False, eval_mode=False, task="obman", grid_mode="reference", return_stats=False,
+                                 normals=False):
     """Hand + object meshes of one sample (utils/mesh.py:17-195): writes <filename>_hand.ply / _obj.ply.
     `max_batch` and `device` are accepted for signature compatibility; chunking is internal to the kernel and
     the decoder's device is used.  `grid_mode="reference"` reproduces the true-division lattice of
@@ -275,8 +367,15 @@ def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, l
     `cls_branch` only makes the reference store a per-voxel class column that nothing reads (utils/mesh.py:59-60,
     111-112); it is accepted and has no effect.  `label_out` runs the label pass over the hand mesh vertices
     (utils/mesh.py:137-184) and needs a decoder with a classifier head.  As in the reference, the object mesh is
-    written with the hand mesh's ICP translation / scale as its offset / scale (utils/mesh.py:123-133,186-195)."""
+    written with the hand mesh's ICP translation / scale as its offset / scale (utils/mesh.py:123-133,186-195).
+    `normals=True`: both files carry per-vertex unit normals (nx / ny / nz) - the analytic SDF gradient of the surface's own head at
+    the vertex, normalised - and the stats dict their `normals_degenerate_hand` / `_obj` counts; a decoder the gradient kernel does
+    not cover raises NotImplementedError before anything is swept."""
     decoder.eval() if hasattr(decoder, "eval") else None
+    evaluator = None
+    if normals:
+        evaluator = decoder_for(decoder, specs, mano_results)
+        require_normals(evaluator)
     # (the volumes go to marching cubes only: a decoder set to the narrow-band fine sweep may use it)
     r = decode_two_pass(hand_branch, obj_branch, decoder, latent_vec, mano_results, obj_results, specs, N, grid_mode, cam_intr,
                         mc_only=True)
@@ -290,5 +389,6 @@ def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, l
         write_label_outputs(vertices, f, labels, filename + "_hand", offset, scale, viz)
         stats["labels"] = labels
 
-    stats = write_hand_and_object(r, filename, hand_branch, obj_branch, offset, scale, eval_mode, task, label_pass if label_out else None)
+    stats = write_hand_and_object(r, filename, hand_branch, obj_branch, offset, scale, eval_mode, task, label_pass if label_out else None,
+                                  normals=evaluator)
     return stats if return_stats else None

@@ -25,6 +25,7 @@ extern "C" {
 #define ASDF_ENOSPC (-5)     /* caller-provided buffer / workspace too small */
 #define ASDF_ERANGE (-6)     /* iso level outside the volume's data range (skimage ValueError) */
 #define ASDF_ENOSURF (-7)    /* no surface found (skimage RuntimeError) */
+#define ASDF_ENOGRAD (-8)    /* asdf_decode_points_grad: a decoder / sample its kernel is not built for */
 
 #define ASDF_MAX_HEADS 2
 #define ASDF_MAX_POINT_FEATS 64
@@ -264,6 +265,17 @@ int asdf_neg_bbox(const float* vol_dev, int32_t n0, int32_t n1, int32_t n2, int3
  * (deep_sdf/utils.py:64-75) for one chunk. */
 int asdf_decode_points(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, float* sdf_hand_dev,
                        float* sdf_obj_dev, void* stream);
+
+/* asdf_decode_points plus the analytic gradient of each SDF with respect to the query coordinates it is given (one forward-mode pass of
+ * the fp32 MFMA chain: a point occupies four columns - its value and the tangents d/dx0, d/dx1, d/dx2).  grad_*_dev are [M][3] fp32.
+ * Any output pointer may be NULL; an MLP both of whose outputs are NULL is not evaluated.  M == 0 is ASDF_OK and launches nothing.
+ * The SDF values are bit-identical to asdf_decode_points under ASDF_MATH_F32; the call always runs on the fp32 chain and neither
+ * reads nor changes the decoder's math mode or MFMA shape.  The derivative of ReLU at 0 is 0, as in torch.
+ * Covered: SeparateDecoder with affine point features (plain xyz and the kinematic embeddings); a part classifier is not evaluated.
+ * ASDF_ENOGRAD for CombinedDecoder, NeRF-encoded point features and a pixel-aligned sample; unbound decoder / bad arguments as
+ * asdf_decode_points. */
+int asdf_decode_points_grad(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, float* sdf_hand_dev, float* grad_hand_dev,
+                            float* sdf_obj_dev, float* grad_obj_dev, void* stream);
 
 /* ---- Arithmetic of the three hidden GEMMs of the grid sweeps (asdf_decode_grid; explicit point lists always run
  * ASDF_MATH_F32 - they have no bbox record to carry the range report below):
