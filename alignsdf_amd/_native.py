@@ -18,7 +18,8 @@ FEATURES_NERF = 1
 ERANGE = -6
 ENOSURF = -7
 ENOGRAD = -8
-ABI_VERSION = 131        # asdf_version() of the library these bindings were written for
+ENOTRACE = -9
+ABI_VERSION = 132        # asdf_version() of the library these bindings were written for
 
 # every symbol include/alignsdf_hip.h declares
 EXPORTS = (
@@ -32,7 +33,7 @@ EXPORTS = (
     "asdf_zoom_cube", "asdf_decode_grid_band_dev", "asdf_decode_grid_dev", "asdf_mc_emit_bounded",
     "asdf_sample_surface_workspace_bytes", "asdf_sample_surface", "asdf_icp_normalise",
     "asdf_decoder_set_sample_host", "asdf_decoder_set_cluster_timeout", "asdf_set_mfma_shape", "asdf_get_mfma_shape",
-    "asdf_debug_pack_host_f16w", "asdf_decoder_set_sample_pixel", "asdf_decode_points_grad",
+    "asdf_debug_pack_host_f16w", "asdf_decoder_set_sample_pixel", "asdf_decode_points_grad", "asdf_trace_rays",
 )
 MATH_F32, MATH_F16X3 = 0, 1
 MAX_CLASSES = 8
@@ -70,6 +71,12 @@ class DecoderSpec(ctypes.Structure):
 
 class HeadParams(ctypes.Structure):
     _fields_ = [("w", ctypes.c_void_p * 5), ("b", ctypes.c_void_p * 5)]
+
+
+class TraceParams(ctypes.Structure):
+    """asdf_trace_params_t"""
+    _fields_ = [("max_steps", ctypes.c_int32), ("refine_steps", ctypes.c_int32), ("step_scale", ctypes.c_float),
+                ("min_step", ctypes.c_float), ("max_step", ctypes.c_float)]
 
 
 _lib = None
@@ -122,6 +129,7 @@ def lib():
     L.asdf_mc_emit_bounded.argtypes = [vp, i32, i32, i32, ctypes.c_double, vp, ctypes.c_size_t, vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp]
     L.asdf_decode_points.argtypes = [vp, vp, i64, vp, vp, vp]
     L.asdf_decode_points_grad.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
+    L.asdf_trace_rays.argtypes = [vp, vp, i64, vp] + [vp] * 8 + [vp]
     L.asdf_decoder_set_classifier.argtypes = [vp, vp, vp, i32]
     L.asdf_decode_points_cls.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     L.asdf_neg_bbox.argtypes = [vp, i32, i32, i32, vp, vp]

@@ -98,6 +98,7 @@ struct asdf_decoder {
   float* pa_cstb;         // [heads][cst floats]: the constants image folded with a zero latent (its c0 / c2 blocks = the biases)
   float* pa_ws;           // [num_cus][kPixelWsFloats] workspace of the pixel-aligned kernel
   float* pa_lat;          // [2][kLatent]: the channel mean of F, zeros
+  unsigned long long* trace_queue;   // [2] device words: the per-head ray queues of asdf_trace_rays (cleared in stream order per call)
 };
 static constexpr int kShortClusters = kClusterCap / kWavePts * kHeads;      // 128
 static constexpr int kNearCap = ASDF_NEAR_CAP;      // near-level refinement list of a split-half sweep
@@ -499,7 +500,7 @@ static int decode_grid_band_impl(asdf_decoder_t* d, int32_t N, const float* orig
 
 extern "C" {
 
-int asdf_version(void) { return 131; }
+int asdf_version(void) { return 132; }
 
 int asdf_set_mfma_shape(int shape) {
   if (shape != 0 && shape != 16 && shape != 32) return ASDF_EINVAL;
@@ -518,6 +519,7 @@ const char* asdf_strerror(int code) {
     case ASDF_ERANGE: return "Surface level must be within volume data range.";
     case ASDF_ENOSURF: return "No surface found at the given iso value.";
     case ASDF_ENOGRAD: return "the gradient kernel does not cover this decoder (SeparateDecoder with affine point features only)";
+    case ASDF_ENOTRACE: return "the ray-tracing kernel does not cover this decoder (SeparateDecoder with affine point features only)";
     default: return "unknown error";
   }
 }
@@ -543,7 +545,8 @@ void asdf_decoder_destroy(asdf_decoder_t* d) {
     if (ev) (void)hipEventDestroy(ev);
   void* bufs[] = {d->stream, d->wlat, d->wpt, d->bias02, d->cst, d->embed, d->cls, d->stream16, d->cst16, d->stream16_hi, d->a16, d->cst16p1,
                   d->pa_proj, d->pa_cstb, d->pa_ws, d->pa_lat, d->shortp.xchg, d->shortp.arrivals, d->band_mark, d->box_aux, d->band_idx,
-                  d->band_count, d->status, d->latent_stage, d->near_idx, d->near_count, d->audit_rec, d->audit_idx, d->audit_count};
+                  d->band_count, d->status, d->latent_stage, d->near_idx, d->near_count, d->audit_rec, d->audit_idx, d->audit_count,
+                  d->trace_queue};
   for (void* b : bufs) (void)hipFree(b);       // (a null pointer is a no-op)
   std::free(d->cst_host);
   std::free(d->cst16_host);
@@ -632,6 +635,8 @@ int asdf_decoder_create(const asdf_decoder_spec_t* spec, const asdf_head_params_
   if (e == hipSuccess) e = k1_cls_prepare();
   if (e == hipSuccess) e = k1pa_prepare();
   if (e == hipSuccess) e = k1g_prepare();
+  if (e == hipSuccess) e = k1t_prepare();
+  if (e == hipSuccess) e = hipMalloc((void**)&d->trace_queue, 2 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc((void**)&d->latent_stage, kLatent * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&d->status, ASDF_STATUS_WORDS * sizeof(int));
   if (e == hipSuccess) e = hipMemset(d->status, 0, ASDF_STATUS_WORDS * sizeof(int));
@@ -964,6 +969,40 @@ int asdf_decode_points_grad(asdf_decoder_t* d, const float* xyz_dev, int64_t M, 
   GradParams g;
   g.grad0 = grad_hand_dev; g.grad1 = grad_obj_dev;
   k1g_launch(p, g, k1g_grid(M, d->num_cus), st);
+  ASDF_HIP(hipGetLastError());
+  return ASDF_OK;
+}
+
+int asdf_trace_rays(asdf_decoder_t* d, const float* rays_dev, int64_t M, const asdf_trace_params_t* params,
+                    float* t_hand_dev, int32_t* status_hand_dev, float* bracket_hand_dev, int32_t* evals_hand_dev,
+                    float* t_obj_dev, int32_t* status_obj_dev, float* bracket_obj_dev, int32_t* evals_obj_dev, void* stream) {
+  if (!d || M < 0 || !params || (M > 0 && !rays_dev)) return ASDF_EINVAL;
+  if (!d->sample_bound) return ASDF_EINVAL;
+  if (params->max_steps < 1 || params->refine_steps < 0 || !(params->min_step > 0.0f) || !(params->max_step > 0.0f)) return ASDF_EINVAL;
+  // (the kernel moves a ray and a bracket as one 16-byte word each)
+  if (((uintptr_t)rays_dev | (uintptr_t)bracket_hand_dev | (uintptr_t)bracket_obj_dev) & 15) return ASDF_EINVAL;
+  // SeparateDecoder with affine point features and an ordinary (per-sample constant) latent
+  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound) return ASDF_ENOTRACE;
+  const bool want0 = t_hand_dev || status_hand_dev, want1 = t_obj_dev || status_obj_dev;
+  if (M == 0 || (!want0 && !want1)) return ASDF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // always the fp32 chain's weights and constants: d->math and the MFMA shape of the split-half sweeps are not looked at
+  DecodeParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.stream = d->stream; p.cst = d->cst;
+  p.P = M; p.N = 1; p.mode = kPointList;
+  p.first_mlp = want0 ? 0 : 1;
+  p.num_mlps = want0 && want1 ? 2 : 1;
+  p.pf = d->spec.point_feats[0];
+  TraceParams q;
+  std::memset(&q, 0, sizeof(q));
+  q.rays = rays_dev; q.M = M;
+  q.rule = TraceRule{params->max_steps, params->refine_steps, params->step_scale, params->min_step, params->max_step};
+  q.out[0] = TraceOutputs{t_hand_dev, status_hand_dev, bracket_hand_dev, evals_hand_dev};
+  q.out[1] = TraceOutputs{t_obj_dev, status_obj_dev, bracket_obj_dev, evals_obj_dev};
+  q.queue = d->trace_queue;
+  ASDF_HIP(hipMemsetAsync(d->trace_queue, 0, 2 * sizeof(unsigned long long), st));
+  k1t_launch(p, q, k1t_grid(M, d->num_cus), st);
   ASDF_HIP(hipGetLastError());
   return ASDF_OK;
 }

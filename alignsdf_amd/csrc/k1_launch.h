@@ -48,6 +48,28 @@ struct GradParams {
 hipError_t k1g_prepare();
 int k1g_grid(long long points, int num_cus);      // workgroups of a launch over `points` points (32 per workgroup tile)
 void k1g_launch(const DecodeParams& p, const GradParams& g, int grid, hipStream_t st);
+// sphere tracing on the fp32 chain (k1t_kernels.hip): one ray per MFMA column, free columns refilled from a per-head queue;
+// SeparateDecoder, affine point features.  The rule: sdf_mlp_trace_kernel.h
+struct TraceRule {
+  int max_steps, refine_steps;
+  float step_scale, min_step, max_step;
+};
+struct TraceOutputs {       // of one head; each may be null
+  float* t;                 // [M] (+inf: MISS)
+  int* status;              // [M] 0 MISS, 1 HIT, 2 INSIDE, 3 EXHAUSTED
+  float* bracket;           // [M][4] (t_lo, t_hi, f_lo, f_hi) of a HIT, zeros otherwise
+  int* evals;               // [M] decoder evaluations the ray took
+};
+struct TraceParams {
+  const float* rays;        // [M][8]: o (3), d (3), t0, t1
+  long long M;
+  TraceRule rule;
+  TraceOutputs out[2];      // hand, object
+  unsigned long long* queue;   // [2] device words, 0 at launch: the next ray of each head's queue
+};
+hipError_t k1t_prepare();
+int k1t_grid(long long rays, int num_cus);        // workgroups of a launch over `rays` rays (128 columns per workgroup)
+void k1t_launch(const DecodeParams& p, const TraceParams& q, int grid, hipStream_t st);
 void k1h_launch(int kp, bool two_out, const DecodeParams& p, int grid, hipStream_t st);
 // the W form (16x16x32 MFMAs) of the SeparateDecoder kernels with affine point features: k1hw_kernels.hip
 hipError_t k1hw_prepare();

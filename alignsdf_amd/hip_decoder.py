@@ -206,6 +206,18 @@ def grad_refusal(combined, point_feat_size, encode_style, pixel_align):
     return None
 
 
+def trace_refusal(combined, point_feat_size, encode_style, pixel_align):
+    """Why (a string) the ray-tracing form of the fp32 chain (HipSdfDecoder.trace_rays, csrc/k1t_kernels.hip) does not cover a decoder
+    of this shape, or None.  Its coverage is the gradient kernel's: SeparateDecoder with point features affine in xyz."""
+    if combined:
+        return "CombinedDecoder (the ray-tracing kernel is built for SeparateDecoder)"
+    if pixel_align:
+        return "pixel-aligned latent (the ray-tracing kernel has no bicubic gather)"
+    if encode_style == "nerf" and int(point_feat_size) > 3:
+        return "NeRF encoding with PointFeatSize %d (only point features affine in xyz are built)" % int(point_feat_size)
+    return None
+
+
 class HipSdfDecoder:
     """Device-resident packed decoder.  One instance per (module, device)."""
 
@@ -1322,6 +1334,46 @@ class HipSdfDecoder:
             raise NotImplementedError("the gradient kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
         _native.check(code, "asdf_decode_points_grad")
         return sh, gh, so, go
+
+    def trace_refusal(self):
+        """trace_refusal() of this decoder: why trace_rays would refuse, or None."""
+        return trace_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
+
+    def trace_rays(self, origins, dirs, t0, t1, hand=True, obj=True, max_steps=64, refine_steps=6, step_scale=1.0, min_step=1e-3,
+                   max_step=0.05, want_bracket=False, want_evals=False):
+        """Sphere tracing inside one kernel (csrc/k1t_kernels.hip; the rule: include/alignsdf_hip.h, asdf_trace_rays): the first
+        surface of each head along the segments origins + t dirs, t0 <= t <= t1 (origins / dirs [M, 3], t0 / t1 [M] or scalars, in
+        the normalised space of decode_points; dirs need not be unit vectors).  Returns {"hand": r, "obj": r}, None for a head
+        switched off, r = {"t" [M] fp32 (+inf: MISS), "status" [M] int32 (render.MISS / HIT / INSIDE / EXHAUSTED), "bracket" [M, 4]
+        (t_lo, t_hi, f_lo, f_hi of a HIT) with want_bracket, "evals" [M] int32 with want_evals} on the device.  Every sdf sampled is
+        decode_points' under set_math("f32"), bit for bit; the math mode of the sweeps is neither read nor changed.
+        NotImplementedError(reason) for a decoder trace_refusal() does not cover (TorchModuleDecoder.trace_rays follows the same
+        rule on the module)."""
+        from .render import pack_rays
+        why = self.trace_refusal()
+        if why is not None:
+            raise NotImplementedError("the ray-tracing kernel does not cover this decoder: %s" % why)
+        rays = pack_rays(origins, dirs, t0, t1, self.device)
+        M = rays.shape[0]
+        res, args = {}, []
+        for name, on in (("hand", hand), ("obj", obj)):
+            r = None
+            if on:
+                r = {"t": torch.empty(M, dtype=torch.float32, device=self.device),
+                     "status": torch.empty(M, dtype=torch.int32, device=self.device)}
+                if want_bracket:
+                    r["bracket"] = torch.empty((M, 4), dtype=torch.float32, device=self.device)
+                if want_evals:
+                    r["evals"] = torch.empty(M, dtype=torch.int32, device=self.device)
+            res[name] = r
+            args += [r[k].data_ptr() if r is not None and k in r else None for k in ("t", "status", "bracket", "evals")]
+        params = _native.TraceParams(int(max_steps), int(refine_steps), float(step_scale), float(min_step), float(max_step))
+        with torch.cuda.device(self.device):
+            code = self._L.asdf_trace_rays(self._h, rays.data_ptr(), M, ctypes.byref(params), *args, self._stream())
+        if code == _native.ENOTRACE:       # (the library's own gate: whatever trace_refusal() missed is still a refusal, not a native error)
+            raise NotImplementedError("the ray-tracing kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
+        _native.check(code, "asdf_trace_rays")
+        return res
 
     def classify_points(self, xyz, want_sdf=True):
         """decode_points plus the part classifier: (hand [M], obj [M], scores [M, num_class], labels [M] int64) - the

@@ -57,7 +57,8 @@ def reconstruct_sample(decoder, specs, latent, mano_results, obj_results, N, mes
 
 def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, end_point, task="obman", device="cuda", scale=None,
                 cube_dim=128, label_out=False, viz=False, eval_mode=False, code_source=None, grid_mode="reference",
-                data_root="data", allow_missing_gt=False, fast=None, stride=1, on_record=None, normals=False):
+                data_root="data", allow_missing_gt=False, fast=None, stride=1, on_record=None, normals=False, render=None,
+                camera_source=None):
     """Reconstruct samples [start_point, end_point) of a split file (reconstruct.py:33-95).  `loaded_model` is the
     decoder module, or any wrapper exposing it as `.module.decoder` / `.decoder` like the reference's DataParallel model.
     `fast`: see pipelined_two_pass (default: ordinary sweeps, every voxel at <= 1e-5).  `stride` > 1: every stride-th sample of the
@@ -65,7 +66,15 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
     (dist_reconstruct keeps its shard's records file current with it).  `normals=True`: every file carries per-vertex unit normals
     (nx / ny / nz: the normalised analytic SDF gradient, see pipelined_two_pass) and every record `normals_degenerate_hand` / `_obj`;
     a decoder the gradient kernel does not cover raises NotImplementedError before the first sweep and before any file is written.
+    `render=(H, W)` with `camera_source(name, index) -> (cam_intr, root_joint)` (render.npz_camera_source / synthetic_camera_source): one
+    H x W view per sample ray-cast straight from the decoder inside the sample's zoom cube - depth, status, part and normal maps in
+    <name>_render.npz next to the meshes (render.render_view) and `render_evals_mean` / `render_exhausted_hand` / `_obj` in every
+    record; without a camera_source it is an error before the first sweep.  A decoder the tracing kernel does not cover (NeRF-encoded
+    features, CombinedDecoder) keeps its native sweeps and is traced on the module path by the same rule (render.view_evaluator).  The meshes are the same files with and without it.
     Returns the list of per-sample records."""
+    if render is not None and camera_source is None:
+        raise ValueError("reconstruct(render=...) needs a camera_source: render.npz_camera_source(<dir of <sample>.npz with cam_intr and "
+                         "root_joint>), or render.synthetic_camera_source(H, W) for synthetic runs")
     stride = max(1, int(stride))
     with open(split_filename, "r") as f:
         names = json.load(f)["filenames"][int(start_point):int(end_point):stride]
@@ -87,6 +96,10 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
             yield ((index, name), *code_source(name, index))
 
     extra = {"normals": True} if normals else {}          # (the option travels only when it is on)
+    if render is not None:
+        from .render import trace_defaults
+        extra["render"] = {"size": (int(render[0]), int(render[1])), "camera": lambda key: camera_source(key[1], key[0]),
+                           "trace": trace_defaults(specs)}
     try:
         with torch.no_grad():
             for (index, name), r in pipelined_two_pass(decoder, specs, samples(), cube_dim, grid_mode, host_copy=True,
@@ -137,6 +150,32 @@ def add_normals_argument(p):
                         "SDF at the vertex, normalised - one forward-mode pass of the decoder per surface.  Default: x y z only")
 
 
+def add_render_arguments(p):
+    p.add_argument("--render", metavar="HxW", default=None,
+                   help="also write <sample>_render.npz next to the meshes: depth, status, part and normal maps of one H x W view per sample, "
+                        "ray-cast straight from the SDF decoder (sphere tracing inside the sample's zoom cube).  Needs a camera: --cameras, "
+                        "or --synthetic")
+    p.add_argument("--cameras", metavar="DIR", default=None,
+                   help="--render: <DIR>/<sample>.npz with cam_intr (3 x 3 or 3 x 4, in the pixels of the view) and root_joint (3)")
+
+
+def render_from_args(args, parser):
+    """{} without --render, else the render / camera_source options of reconstruct(); --render without a camera is an error here, before
+    anything is loaded."""
+    if not args.render:
+        return {}
+    from . import render as rd
+    try:
+        size = rd.parse_size(args.render)
+    except ValueError as e:
+        parser.error(str(e))
+    if args.cameras:
+        return {"render": size, "camera_source": rd.npz_camera_source(args.cameras)}
+    if getattr(args, "synthetic", False):
+        return {"render": size, "camera_source": rd.synthetic_camera_source(*size)}
+    parser.error("--render needs a camera: pass --cameras <dir of <sample>.npz with cam_intr and root_joint> (or --synthetic)")
+
+
 def apply_sweep_arguments(args):
     if args.coarse:
         os.environ["ASDF_COARSE"] = args.coarse          # read when the decoder is packed
@@ -160,7 +199,9 @@ def main(argv=None):
     p.add_argument("--cube_dim", type=int, default=128, help="grid resolution (reference CLI hard-codes 128, reconstruct.py:178)")
     add_sweep_arguments(p)
     add_normals_argument(p)
+    add_render_arguments(p)
     args = p.parse_args(argv)
+    render = render_from_args(args, p)
     apply_sweep_arguments(args)
     split = args.split_filename or {"obman": "input/obman.json", "dexycb": "input/dexycb.json"}[args.task]
     output_dir = os.path.join(args.model_directory, "Eval_" + args.task)
@@ -172,7 +213,7 @@ def main(argv=None):
     source = code_source_from_args(args, specs, p)
     return reconstruct(decoder, specs, split, output_dir, args.start_point, args.end_point, task=args.task, cube_dim=args.cube_dim,
                        label_out=args.label_out, viz=args.viz, eval_mode=args.eval_mode, code_source=source,
-                       allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None, normals=args.normals)
+                       allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None, normals=args.normals, **render)
 
 
 if __name__ == "__main__":

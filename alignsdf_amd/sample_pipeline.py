@@ -10,7 +10,7 @@ from .utils import mesh as mesh_utils, utils
 
 
 def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_copy=False, label_out=False, midpoint=None, report=None,
-                       fast=None, normals=False):
+                       fast=None, normals=False, render=None):
     """Software pipeline over independent samples.  `samples` yields (key, latent, mano_results, obj_results); the
     generator yields (key, result) in order, where result holds the pass-2 volumes (device), the zoom cube and the
     marching-cubes output per enabled branch (`verts_*`, `faces_*` device tensors, absent when MC found no surface).
@@ -45,8 +45,13 @@ def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_c
     device, `host_kept_normals_*` at input capacity with the other copies.  The sample is re-bound first, as for the label pass.  A
     decoder the gradient kernel does not cover raises NotImplementedError before the first sweep.
 
+    render = {"size": (H, W), "camera": key -> (cam_intr, root_joint), "trace": parameters of trace_rays} runs the render pass where the
+    normal pass runs, with the same re-bind: one view of the sample ray-cast from the decoder inside the sample's zoom cube
+    (render.render_view; a decoder the tracing kernel refuses is traced on the module path, render.view_evaluator, chosen before the
+    first sweep) - `render` in the result (its maps on the device), `host_render_*` with host_copy.
+
     report, if given (a dict), receives the evaluator that ran and a snapshot of its sweep counters (see write_sweeps_json)."""
-    yield from SamplePipeline(decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals).run()
+    yield from SamplePipeline(decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals, render).run()
 
 
 @dataclasses.dataclass(slots=True, eq=False)
@@ -64,9 +69,9 @@ class InFlight:
 class SamplePipeline:
     """pipelined_two_pass: the decoder and the state its stages share, one method per stage, and the window over the samples (run)."""
 
-    def __init__(self, decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals=False):
+    def __init__(self, decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals=False, render=None):
         self.specs, self.N, self.host_copy, self.label_out, self.midpoint = specs, N, host_copy, label_out, midpoint
-        self.normals = bool(normals)
+        self.normals, self.render = bool(normals), render
         self.samples = (InFlight(key, codes) for key, *codes in samples)   # (lazy: a sample is fetched when the window asks for it)
         self.head = next(self.samples, None)
         if self.head is None:                      # (an empty stream: no decoder is asked for)
@@ -75,6 +80,11 @@ class SamplePipeline:
         self.hip = hip = utils.decoder_for(decoder, specs, self.head.codes[1])
         if self.normals:
             mesh_utils.require_normals(hip)        # (before the first sweep: no run of files without the normals that were asked for)
+        if self.render is not None:
+            # (before the first sweep as well: the evaluator the views are traced on - `hip`, or the module for a decoder whose sweeps
+            # are native and which the tracing kernel refuses)
+            from .render import view_evaluator
+            self.view_eval = view_evaluator(hip, decoder, specs)
         if fast is not None and hasattr(hip, "set_fast"):
             hip.set_fast(bool(fast))
         if report is not None:                     # (the caller's `sweeps.json`: which evaluator ran, and its counters at the start)
@@ -186,8 +196,28 @@ class SamplePipeline:
         return done
 
     def post_process(self, s):
-        """Label pass, component filter, normal pass and host copies of the surfaces marching cubes found."""
+        """Label pass, component filter, normal pass and host copies of the surfaces marching cubes found; the render pass."""
         r = s.result
+        self.post_process_surfaces(s, r)
+        if self.render is not None:
+            # one view of the sample, marched inside its zoom cube (the region the meshes come from: the field far outside the clamp is
+            # unconstrained) - the decoder holds the next sample's constants by now
+            from .render import render_view
+            if self.view_eval is not self.hip:
+                utils.bind_sample(self.view_eval, self.specs, *s.codes)
+            elif self.bound is not s:
+                self.bind(s)
+            H, W = self.render["size"]
+            lo = [float(v) for v in r["origin"]]
+            hi = [v + (self.N - 1) * float(r["voxel_size"]) for v in lo]
+            view = render_view(self.view_eval, *self.render["camera"](s.key), self.specs["SdfScaleFactor"], H, W, box=(lo, hi), **self.render["trace"])
+            r["render"] = dict(view, size=(H, W), trace=dict(self.render["trace"]))
+            if self.host_copy:
+                for name, t in view.items():
+                    r["copy_done_render"] = self.to_host(r, "render_" + name, t)
+
+    def post_process_surfaces(self, s, r):
+        """The per-surface part of post_process."""
         for _, part in self.parts:
             if "verts_" + part not in r:
                 continue

@@ -47,6 +47,11 @@ class FileWriter:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         self.jobs.append((path, self.pool.submit(write_ply, path, verts, faces, normals)))
 
+    def write_view(self, path, view, H, W, trace):
+        from .render import save_view
+        self.poll()
+        self.jobs.append((path, self.pool.submit(save_view, path, view, H, W, trace)))
+
     def close(self, failing=False):
         from .frontend import restore_gil_handover
         self.pool.shutdown(wait=True)
@@ -131,6 +136,17 @@ class SampleWriter:
             self.writer.write_ply(base + ".ply", points, faces)
         return trans, icp_scale
 
+    def write_render(self, path, r, rec):
+        """<name>_render.npz next to the meshes: the maps of the sample's view (pipelined_two_pass(render=...)), and its statistics in
+        the record."""
+        from .render import VIEW_MAPS, VIEW_STATS
+        r["copy_done_render"].synchronize()
+        H, W = r["render"]["size"]
+        view = {k: r["host_render_" + k].numpy() for k in VIEW_MAPS + VIEW_STATS if "host_render_" + k in r}
+        rec["render_evals_mean"] = float(view["evals_mean"])
+        rec["render_exhausted_hand"], rec["render_exhausted_obj"] = int(view["exhausted_hand"]), int(view["exhausted_obj"])
+        self.writer.write_view(path, view, H, W, r["render"]["trace"])
+
     def write_labels(self, base, r, rec, offset, scale):
         verts, faces, vertices = mesh_utils.place_vertices(r["host_verts_hand"], r["host_faces_hand"], r["origin"], r["voxel_size"])
         labels = r["host_labels_hand"].float()
@@ -157,6 +173,8 @@ class SampleWriter:
                 rec["icp_trans"], rec["icp_scale"] = np.asarray(offset).reshape(-1).tolist(), float(np.asarray(sc).reshape(-1)[0])
                 if "host_labels_hand" in r:
                     self.write_labels(base, r, rec, offset, sc)
+        if "render" in r:
+            self.write_render(self.path(name, "render") + ".npz", r, rec)
         now = time.perf_counter()
         rec["seconds"], self.t_prev = now - self.t_prev, now
         self.records.append(rec)

@@ -287,6 +287,34 @@ class TorchModuleDecoder:
             module.train(was_training)
         return tuple(out)
 
+    def trace_rays(self, origins, dirs, t0, t1, hand=True, obj=True, max_steps=64, refine_steps=6, step_scale=1.0, min_step=1e-3,
+                   max_step=0.05, want_bracket=False, want_evals=False):
+        """The interface and the rule of HipSdfDecoder.trace_rays on the module (render.trace_lockstep): per head, all rays in lockstep
+        under masks, one module call per step.  Covers every variant the module path covers.  A head the module does not have is None."""
+        from .render import pack_rays, trace_lockstep
+        if self._sample is None:
+            raise ValueError("no sample bound: call set_sample first")
+        rays = pack_rays(origins, dirs, t0, t1, self.device)
+        res = {}
+        for k, (name, on) in enumerate((("hand", hand), ("obj", obj))):
+            res[name] = None
+            if not on:
+                continue
+            absent = []
+
+            def sdf_of(points, k=k):
+                v = self._decode(points)[k]
+                if v is None:
+                    absent.append(True)
+                    return torch.ones(points.shape[0], dtype=torch.float32, device=self.device)
+                return v
+            with torch.no_grad():
+                r = trace_lockstep(sdf_of, rays, max_steps, refine_steps, step_scale, min_step, max_step)
+            if absent:
+                continue
+            res[name] = {key: r[key] for key, keep in (("t", True), ("status", True), ("bracket", want_bracket), ("evals", want_evals)) if keep}
+        return res
+
     def classify_points(self, xyz, want_sdf=True):
         if not self.num_class:
             raise ValueError("this decoder has no classifier_head (specs['ClassifierBranch'] is off)")

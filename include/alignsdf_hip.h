@@ -26,6 +26,7 @@ extern "C" {
 #define ASDF_ERANGE (-6)     /* iso level outside the volume's data range (skimage ValueError) */
 #define ASDF_ENOSURF (-7)    /* no surface found (skimage RuntimeError) */
 #define ASDF_ENOGRAD (-8)    /* asdf_decode_points_grad: a decoder / sample its kernel is not built for */
+#define ASDF_ENOTRACE (-9)   /* asdf_trace_rays: a decoder / sample its kernel is not built for */
 
 #define ASDF_MAX_HEADS 2
 #define ASDF_MAX_POINT_FEATS 64
@@ -276,6 +277,41 @@ int asdf_decode_points(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, flo
  * asdf_decode_points. */
 int asdf_decode_points_grad(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, float* sdf_hand_dev, float* grad_hand_dev,
                             float* sdf_obj_dev, float* grad_obj_dev, void* stream);
+
+/* Sphere tracing: the first surface of each head along M ray segments, marched and refined inside one kernel (csrc/k1t_kernels.hip -
+ * a ray per column of the fp32 MFMA chain; a column whose ray is done takes the next ray of a device queue).  No counterpart in the
+ * reference (it only ever meshes).  rays_dev [M][8] fp32, 16-byte aligned: origin (3), direction (3, need not be a unit vector), t0, t1 -
+ * positions o + t d in the decoder's normalised space.  The rule, all in fp32 with every operation rounded on its own:
+ *   start   o, d, t0, t1 not all finite or t0 > t1: MISS, 0 evaluations.  Else t = t0.
+ *   MARCH   sample f at t.  f <= 0: on the first sample INSIDE with t = t0; else the bracket is (t_prev, f_prev) .. (t, f) and the ray
+ *           is refined.  f > 0: t == t1 -> MISS (the end of the segment is always sampled, exactly); the max_steps-th such sample ->
+ *           EXHAUSTED with its t; else t = min(t + clamp(step_scale f, min_step, max_step), t1).
+ *   REFINE  up to refine_steps bisections (the midpoint replaces the hi end if f <= 0, else the lo end; stops early when the midpoint
+ *           equals an end), then t = clamp(t_lo + (t_hi - t_lo) f_lo / (f_lo - f_hi), t_lo, t_hi): HIT.
+ * Outputs per head, each may be NULL (a head whose t and status are both NULL is not evaluated): t [M] (+inf for MISS), status [M]
+ * (ASDF_TRACE_*), bracket [M][4] = (t_lo, t_hi, f_lo, f_hi) of a HIT (zeros otherwise; 16-byte aligned), evals [M] = decoder
+ * evaluations the ray took (<= max_steps + refine_steps + 1).  Every sdf the kernel samples is asdf_decode_points' under ASDF_MATH_F32,
+ * bit for bit; the call neither reads nor changes the decoder's math mode or MFMA shape.  M == 0 is ASDF_OK and launches nothing.
+ * ASDF_EINVAL: NULL decoder, no sample bound, M < 0, NULL / misaligned rays, NULL params, max_steps < 1, refine_steps < 0, min_step or
+ * max_step not > 0.  ASDF_ENOTRACE: CombinedDecoder, NeRF-encoded point features, a pixel-aligned sample.
+ * Not re-entrant per decoder: the two queue words belong to the decoder and are cleared in `stream` order, so calls on one decoder go
+ * through one stream at a time (as every other call that uses the decoder's device scratch).
+ * Sphere tracing promises what the field does: a step can jump a feature thinner than the step, and a learned field is only
+ * approximately a distance - step_scale < 1 and max_step at the field's clamping distance are the caller's margins. */
+#define ASDF_TRACE_MISS 0
+#define ASDF_TRACE_HIT 1
+#define ASDF_TRACE_INSIDE 2
+#define ASDF_TRACE_EXHAUSTED 3
+typedef struct asdf_trace_params {
+  int32_t max_steps;    /* MARCH samples with f > 0 before a ray is EXHAUSTED (>= 1) */
+  int32_t refine_steps; /* bisections of the bracket (>= 0) */
+  float step_scale;     /* step = step_scale * f ... */
+  float min_step;       /* ... clamped to [min_step, max_step] (both > 0) */
+  float max_step;
+} asdf_trace_params_t;
+int asdf_trace_rays(asdf_decoder_t* dec, const float* rays_dev, int64_t M, const asdf_trace_params_t* params,
+                    float* t_hand_dev, int32_t* status_hand_dev, float* bracket_hand_dev, int32_t* evals_hand_dev,
+                    float* t_obj_dev, int32_t* status_obj_dev, float* bracket_obj_dev, int32_t* evals_obj_dev, void* stream);
 
 /* ---- Arithmetic of the three hidden GEMMs of the grid sweeps (asdf_decode_grid; explicit point lists always run
  * ASDF_MATH_F32 - they have no bbox record to carry the range report below):
