@@ -19,7 +19,8 @@ ERANGE = -6
 ENOSURF = -7
 ENOGRAD = -8
 ENOTRACE = -9
-ABI_VERSION = 132        # asdf_version() of the library these bindings were written for
+ENOPROJECT = -10
+ABI_VERSION = 132       # asdf_version() of the library these bindings were written for
 
 # every symbol include/alignsdf_hip.h declares
 EXPORTS = (
@@ -34,6 +35,7 @@ EXPORTS = (
     "asdf_sample_surface_workspace_bytes", "asdf_sample_surface", "asdf_icp_normalise",
     "asdf_decoder_set_sample_host", "asdf_decoder_set_cluster_timeout", "asdf_set_mfma_shape", "asdf_get_mfma_shape",
     "asdf_debug_pack_host_f16w", "asdf_decoder_set_sample_pixel", "asdf_decode_points_grad", "asdf_trace_rays",
+    "asdf_project_points",
 )
 MATH_F32, MATH_F16X3 = 0, 1
 MAX_CLASSES = 8
@@ -77,6 +79,11 @@ class TraceParams(ctypes.Structure):
     """asdf_trace_params_t"""
     _fields_ = [("max_steps", ctypes.c_int32), ("refine_steps", ctypes.c_int32), ("step_scale", ctypes.c_float),
                 ("min_step", ctypes.c_float), ("max_step", ctypes.c_float)]
+
+
+class ProjectParams(ctypes.Structure):
+    """asdf_project_params_t"""
+    _fields_ = [("max_iters", ctypes.c_int32), ("tol", ctypes.c_float), ("max_move", ctypes.c_float), ("min_grad2", ctypes.c_float)]
 
 
 _lib = None
@@ -130,6 +137,7 @@ def lib():
     L.asdf_decode_points.argtypes = [vp, vp, i64, vp, vp, vp]
     L.asdf_decode_points_grad.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     L.asdf_trace_rays.argtypes = [vp, vp, i64, vp] + [vp] * 8 + [vp]
+    L.asdf_project_points.argtypes = [vp, vp, i64, i32, vp] + [vp] * 6 + [vp]
     L.asdf_decoder_set_classifier.argtypes = [vp, vp, vp, i32]
     L.asdf_decode_points_cls.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     L.asdf_neg_bbox.argtypes = [vp, i32, i32, i32, vp, vp]

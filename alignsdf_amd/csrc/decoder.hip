@@ -500,7 +500,7 @@ static int decode_grid_band_impl(asdf_decoder_t* d, int32_t N, const float* orig
 
 extern "C" {
 
-int asdf_version(void) { return 132; }
+int asdf_version(void) { return 132; }      // (asdf_project_points is an addition: no existing call changed)
 
 int asdf_set_mfma_shape(int shape) {
   if (shape != 0 && shape != 16 && shape != 32) return ASDF_EINVAL;
@@ -520,6 +520,7 @@ const char* asdf_strerror(int code) {
     case ASDF_ENOSURF: return "No surface found at the given iso value.";
     case ASDF_ENOGRAD: return "the gradient kernel does not cover this decoder (SeparateDecoder with affine point features only)";
     case ASDF_ENOTRACE: return "the ray-tracing kernel does not cover this decoder (SeparateDecoder with affine point features only)";
+    case ASDF_ENOPROJECT: return "the projection kernel does not cover this decoder (SeparateDecoder with affine point features only)";
     default: return "unknown error";
   }
 }
@@ -636,6 +637,7 @@ int asdf_decoder_create(const asdf_decoder_spec_t* spec, const asdf_head_params_
   if (e == hipSuccess) e = k1pa_prepare();
   if (e == hipSuccess) e = k1g_prepare();
   if (e == hipSuccess) e = k1t_prepare();
+  if (e == hipSuccess) e = k1p_prepare();
   if (e == hipSuccess) e = hipMalloc((void**)&d->trace_queue, 2 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc((void**)&d->latent_stage, kLatent * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&d->status, ASDF_STATUS_WORDS * sizeof(int));
@@ -1003,6 +1005,35 @@ int asdf_trace_rays(asdf_decoder_t* d, const float* rays_dev, int64_t M, const a
   q.queue = d->trace_queue;
   ASDF_HIP(hipMemsetAsync(d->trace_queue, 0, 2 * sizeof(unsigned long long), st));
   k1t_launch(p, q, k1t_grid(M, d->num_cus), st);
+  ASDF_HIP(hipGetLastError());
+  return ASDF_OK;
+}
+
+int asdf_project_points(asdf_decoder_t* d, const float* xyz_dev, int64_t M, int32_t head, const asdf_project_params_t* params,
+                        float* xyz_out_dev, float* sdf_dev, float* grad_dev, float* sdf_in_dev, int32_t* status_dev, int32_t* evals_dev,
+                        void* stream) {
+  if (!d || M < 0 || (M > 0 && !xyz_dev) || !params) return ASDF_EINVAL;
+  if (!d->sample_bound) return ASDF_EINVAL;
+  if (params->max_iters < 0 || !(params->tol >= 0.0f) || !(params->max_move > 0.0f) || !(params->min_grad2 > 0.0f)) return ASDF_EINVAL;
+  // SeparateDecoder with affine point features and an ordinary (per-sample constant) latent
+  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound) return ASDF_ENOPROJECT;
+  if (head < 0 || head >= d->spec.num_heads) return ASDF_EINVAL;
+  if (M == 0) return ASDF_OK;
+  if (!xyz_out_dev && !sdf_dev && !grad_dev && !sdf_in_dev && !status_dev && !evals_dev) return ASDF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // always the fp32 chain's weights and constants: d->math and the MFMA shape of the split-half sweeps are not looked at
+  DecodeParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.stream = d->stream; p.cst = d->cst;
+  p.xyz = xyz_dev; p.P = M; p.N = 1; p.mode = kPointList;
+  p.first_mlp = head;
+  p.num_mlps = 1;
+  p.pf = d->spec.point_feats[0];
+  ProjectParams q;
+  std::memset(&q, 0, sizeof(q));
+  q.rule = ProjectRule{params->max_iters, params->tol, params->max_move, params->min_grad2};
+  q.xyz_out = xyz_out_dev; q.sdf = sdf_dev; q.grad = grad_dev; q.sdf_in = sdf_in_dev; q.status = status_dev; q.evals = evals_dev;
+  k1p_launch(p, q, k1p_grid(M, d->num_cus), st);
   ASDF_HIP(hipGetLastError());
   return ASDF_OK;
 }

@@ -70,6 +70,24 @@ struct TraceParams {
 hipError_t k1t_prepare();
 int k1t_grid(long long rays, int num_cus);        // workgroups of a launch over `rays` rays (128 columns per workgroup)
 void k1t_launch(const DecodeParams& p, const TraceParams& q, int grid, hipStream_t st);
+// Newton projection onto one head's zero level on the fp32 chain (k1p_kernels.hip): the gradient form's quad of columns, iterated
+// per workgroup tile while a point of it is live; SeparateDecoder, affine point features.  The rule: sdf_mlp_project_kernel.h
+struct ProjectRule {
+  int max_iters;
+  float tol, max_move, min_grad2;
+};
+struct ProjectParams {      // the input positions are DecodeParams::xyz [P][3], the head DecodeParams::first_mlp; each output may be null
+  ProjectRule rule;
+  float* xyz_out;           // [P][3] the last iterate
+  float* sdf;               // [P] and
+  float* grad;              // [P][3] at xyz_out
+  float* sdf_in;            // [P] at the input position
+  int* status;              // [P] 0 CONVERGED, 1 SPENT, 2 STALLED, 3 BAD
+  int* evals;               // [P] decoder evaluations the point took
+};
+hipError_t k1p_prepare();
+int k1p_grid(long long points, int num_cus);      // workgroups of a launch over `points` points (32 per workgroup tile)
+void k1p_launch(const DecodeParams& p, const ProjectParams& q, int grid, hipStream_t st);
 void k1h_launch(int kp, bool two_out, const DecodeParams& p, int grid, hipStream_t st);
 // the W form (16x16x32 MFMAs) of the SeparateDecoder kernels with affine point features: k1hw_kernels.hip
 hipError_t k1hw_prepare();

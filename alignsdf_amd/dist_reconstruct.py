@@ -495,6 +495,7 @@ def main(argv=None):
                         "strided (rank, rank + W, ...: spreads a stretch of expensive samples over the ranks)")
     rc.add_sweep_arguments(p)       # --fast / --coarse / --fine: ordinary sweeps (every voxel at <= 1e-5) unless the caller opts in
     rc.add_normals_argument(p)      # --normals: per-vertex unit normals in every file
+    rc.add_polish_argument(p)       # --polish: the vertices of every file moved onto the zero level of the SDF
     rc.add_render_arguments(p)      # --render HxW [--cameras DIR]: one ray-cast view per sample
     args = p.parse_args(argv)
     render = rc.render_from_args(args, p)
@@ -534,7 +535,7 @@ def main(argv=None):
             recs = rc.reconstruct(decoder, specs, split, output_dir, start, end, task=args.task, cube_dim=args.cube_dim,
                                   eval_mode=True, label_out=args.optim, code_source=source, data_root=args.data_root,
                                   allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None, stride=stride,
-                                  on_record=progress, normals=args.normals, **render)
+                                  on_record=progress, normals=args.normals, **({"polish": True} if args.polish else {}), **render)
         except Exception as e:
             for r in getattr(e, "partial_records", []) or []:
                 r["milliseconds"] = 1e3 * r.get("seconds", 0.0)

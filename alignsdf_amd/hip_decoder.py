@@ -218,6 +218,18 @@ def trace_refusal(combined, point_feat_size, encode_style, pixel_align):
     return None
 
 
+def project_refusal(combined, point_feat_size, encode_style, pixel_align):
+    """Why (a string) the projection form of the fp32 chain (HipSdfDecoder.project_points, csrc/k1p_kernels.hip) does not cover a
+    decoder of this shape, or None.  Its coverage is the gradient kernel's: SeparateDecoder with point features affine in xyz."""
+    if combined:
+        return "CombinedDecoder (the projection kernel is built for SeparateDecoder)"
+    if pixel_align:
+        return "pixel-aligned latent (the bicubic gather is not differentiated)"
+    if encode_style == "nerf" and int(point_feat_size) > 3:
+        return "NeRF encoding with PointFeatSize %d (only point features affine in xyz are built)" % int(point_feat_size)
+    return None
+
+
 class HipSdfDecoder:
     """Device-resident packed decoder.  One instance per (module, device)."""
 
@@ -1373,6 +1385,38 @@ class HipSdfDecoder:
         if code == _native.ENOTRACE:       # (the library's own gate: whatever trace_refusal() missed is still a refusal, not a native error)
             raise NotImplementedError("the ray-tracing kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
         _native.check(code, "asdf_trace_rays")
+        return res
+
+    def project_refusal(self):
+        """project_refusal() of this decoder: why project_points would refuse, or None."""
+        return project_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
+
+    def project_points(self, xyz, head, max_iters=8, tol=1e-6, max_move=2.0 / 127, min_grad2=1e-12):
+        """Newton projection onto the zero level of one head inside one kernel (csrc/k1p_kernels.hip; the rule: include/alignsdf_hip.h,
+        asdf_project_points): xyz [M, 3] in the normalised space of decode_points, head 0 / "hand" or 1 / "obj", max_move the
+        per-axis trust box around the input position (default: a voxel of a 128-lattice over [-1, 1]).  Returns a dict of device
+        tensors: "xyz_out" [M, 3] the last iterate, "sdf" [M] and "grad" [M, 3] there, "sdf_in" [M], "status" [M] int32
+        (project.CONVERGED / SPENT / STALLED / BAD), "evals" [M] int32.  Every evaluation is decode_points' under set_math("f32") and
+        decode_points_grad's, bit for bit; the math mode of the sweeps is neither read nor changed.  NotImplementedError(reason) for a
+        decoder project_refusal() does not cover (TorchModuleDecoder.project_points follows the same rule on the module)."""
+        from .project import check_rule, head_index
+        why = self.project_refusal()
+        if why is not None:
+            raise NotImplementedError("the projection kernel does not cover this decoder: %s" % why)
+        h = head_index(head)
+        check_rule(max_iters, tol, max_move, min_grad2)
+        xyz = xyz.detach().to(device=self.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+        M = xyz.shape[0]
+        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=self.device)
+        res = {"xyz_out": new(torch.float32, M, 3), "sdf": new(torch.float32, M), "grad": new(torch.float32, M, 3),
+               "sdf_in": new(torch.float32, M), "status": new(torch.int32, M), "evals": new(torch.int32, M)}
+        params = _native.ProjectParams(int(max_iters), float(tol), float(max_move), float(min_grad2))
+        with torch.cuda.device(self.device):
+            code = self._L.asdf_project_points(self._h, xyz.data_ptr(), M, h, ctypes.byref(params),
+                                               *[t.data_ptr() for t in res.values()], self._stream())
+        if code == _native.ENOPROJECT:     # (the library's own gate: whatever project_refusal() missed is still a refusal, not a native error)
+            raise NotImplementedError("the projection kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
+        _native.check(code, "asdf_project_points")
         return res
 
     def classify_points(self, xyz, want_sdf=True):

@@ -58,7 +58,7 @@ def reconstruct_sample(decoder, specs, latent, mano_results, obj_results, N, mes
 def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, end_point, task="obman", device="cuda", scale=None,
                 cube_dim=128, label_out=False, viz=False, eval_mode=False, code_source=None, grid_mode="reference",
                 data_root="data", allow_missing_gt=False, fast=None, stride=1, on_record=None, normals=False, render=None,
-                camera_source=None):
+                camera_source=None, polish=False):
     """Reconstruct samples [start_point, end_point) of a split file (reconstruct.py:33-95).  `loaded_model` is the
     decoder module, or any wrapper exposing it as `.module.decoder` / `.decoder` like the reference's DataParallel model.
     `fast`: see pipelined_two_pass (default: ordinary sweeps, every voxel at <= 1e-5).  `stride` > 1: every stride-th sample of the
@@ -71,6 +71,11 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
     <name>_render.npz next to the meshes (render.render_view) and `render_evals_mean` / `render_exhausted_hand` / `_obj` in every
     record; without a camera_source it is an error before the first sweep.  A decoder the tracing kernel does not cover (NeRF-encoded
     features, CombinedDecoder) keeps its native sweeps and is traced on the module path by the same rule (render.view_evaluator).  The meshes are the same files with and without it.
+    `polish=True`: the kept vertices of every surface are moved onto the zero level of their own head before anything else reads them
+    (Newton projection inside one kernel, see pipelined_two_pass) - same faces and vertex count, and every record gains
+    `polish_hand` / `polish_obj` = {"converged", "spent", "stalled", "bad", "kept"}: vertices by status of the projection, and how many
+    stayed at their marching-cubes position; an evaluator that cannot project raises NotImplementedError before the first sweep and
+    before any file is written.
     Returns the list of per-sample records."""
     if render is not None and camera_source is None:
         raise ValueError("reconstruct(render=...) needs a camera_source: render.npz_camera_source(<dir of <sample>.npz with cam_intr and "
@@ -96,6 +101,8 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
             yield ((index, name), *code_source(name, index))
 
     extra = {"normals": True} if normals else {}          # (the option travels only when it is on)
+    if polish:
+        extra["polish"] = True
     if render is not None:
         from .render import trace_defaults
         extra["render"] = {"size": (int(render[0]), int(render[1])), "camera": lambda key: camera_source(key[1], key[0]),
@@ -150,6 +157,13 @@ def add_normals_argument(p):
                         "SDF at the vertex, normalised - one forward-mode pass of the decoder per surface.  Default: x y z only")
 
 
+def add_polish_argument(p):
+    p.add_argument("--polish", action="store_true",
+                   help="move the vertices of every written mesh onto the zero level of the SDF (a few Newton steps per vertex inside one "
+                        "kernel, at most one voxel per axis): the residual of marching cubes' linear interpolation goes away, faces "
+                        "and vertex count stay.  Default: the marching-cubes positions")
+
+
 def add_render_arguments(p):
     p.add_argument("--render", metavar="HxW", default=None,
                    help="also write <sample>_render.npz next to the meshes: depth, status, part and normal maps of one H x W view per sample, "
@@ -199,6 +213,7 @@ def main(argv=None):
     p.add_argument("--cube_dim", type=int, default=128, help="grid resolution (reference CLI hard-codes 128, reconstruct.py:178)")
     add_sweep_arguments(p)
     add_normals_argument(p)
+    add_polish_argument(p)
     add_render_arguments(p)
     args = p.parse_args(argv)
     render = render_from_args(args, p)
@@ -213,7 +228,8 @@ def main(argv=None):
     source = code_source_from_args(args, specs, p)
     return reconstruct(decoder, specs, split, output_dir, args.start_point, args.end_point, task=args.task, cube_dim=args.cube_dim,
                        label_out=args.label_out, viz=args.viz, eval_mode=args.eval_mode, code_source=source,
-                       allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None, normals=args.normals, **render)
+                       allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None, normals=args.normals,
+                       **({"polish": True} if args.polish else {}), **render)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ from .utils import mesh as mesh_utils, utils
 
 
 def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_copy=False, label_out=False, midpoint=None, report=None,
-                       fast=None, normals=False, render=None):
+                       fast=None, normals=False, render=None, polish=False):
     """Software pipeline over independent samples.  `samples` yields (key, latent, mano_results, obj_results); the
     generator yields (key, result) in order, where result holds the pass-2 volumes (device), the zoom cube and the
     marching-cubes output per enabled branch (`verts_*`, `faces_*` device tensors, absent when MC found no surface).
@@ -50,8 +50,16 @@ def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_c
     (render.render_view; a decoder the tracing kernel refuses is traced on the module path, render.view_evaluator, chosen before the
     first sweep) - `render` in the result (its maps on the device), `host_render_*` with host_copy.
 
+    polish=True (with host_copy) runs the polish pass right behind K8 and BEFORE the normal pass, the host copies and the eval-mode
+    hook: every kept vertex is moved onto the zero level of its surface's own head by Newton projection inside one kernel
+    (project.polish_vertices: project_points at origin + v * voxel_size with a trust box of one fine voxel per axis; a vertex keeps its
+    marching-cubes position where the projection is BAD or STALLED or ends with a larger |sdf| than it began with).  The kept vertices
+    everything downstream sees - surface sampling and ICP, normals, files - are the polished ones; faces are untouched.  The counts by
+    status and of vertices kept in place: `polish_counts_*` on the device, `host_polish_counts_*` with the other copies.  The sample
+    is re-bound first, as for the normal pass.  A decoder that cannot project raises NotImplementedError before the first sweep.
+
     report, if given (a dict), receives the evaluator that ran and a snapshot of its sweep counters (see write_sweeps_json)."""
-    yield from SamplePipeline(decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals, render).run()
+    yield from SamplePipeline(decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals, render, polish).run()
 
 
 @dataclasses.dataclass(slots=True, eq=False)
@@ -69,9 +77,9 @@ class InFlight:
 class SamplePipeline:
     """pipelined_two_pass: the decoder and the state its stages share, one method per stage, and the window over the samples (run)."""
 
-    def __init__(self, decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals=False, render=None):
+    def __init__(self, decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals=False, render=None, polish=False):
         self.specs, self.N, self.host_copy, self.label_out, self.midpoint = specs, N, host_copy, label_out, midpoint
-        self.normals, self.render = bool(normals), render
+        self.normals, self.render, self.polish = bool(normals), render, bool(polish)
         self.samples = (InFlight(key, codes) for key, *codes in samples)   # (lazy: a sample is fetched when the window asks for it)
         self.head = next(self.samples, None)
         if self.head is None:                      # (an empty stream: no decoder is asked for)
@@ -80,6 +88,9 @@ class SamplePipeline:
         self.hip = hip = utils.decoder_for(decoder, specs, self.head.codes[1])
         if self.normals:
             mesh_utils.require_normals(hip)        # (before the first sweep: no run of files without the normals that were asked for)
+        if self.polish:
+            from .project import require_polish
+            require_polish(hip)                    # (before the first sweep as well)
         if self.render is not None:
             # (before the first sweep as well: the evaluator the views are traced on - `hip`, or the module for a decoder whose sweeps
             # are native and which the tracing kernel refuses)
@@ -232,8 +243,19 @@ class SamplePipeline:
                 # surface when the label pass needs every vertex
                 from .mesh_post import keep_largest_component_device
                 kv, kf, counts = keep_largest_component_device(v, f, r["voxel_size"], r["origin"])
+                polished = None
+                if self.polish:
+                    # the polish pass, on the kept vertices (rows past the kept count hold no vertex: they are projected along, never
+                    # counted and never read) - the decoder holds the next sample's constants by now
+                    from .project import polish_vertices
+                    if self.bound is not s:
+                        self.bind(s)
+                    kv, polished = polish_vertices(self.hip, kv, r["origin"], r["voxel_size"], part, count=counts[0])
+                    r["polish_counts_" + part] = polished
                 r["kept_dev_" + part] = (kv, kf, counts)       # (the eval-mode hook samples the kept surface on the device)
                 copies = {"kept_verts_": kv, "kept_faces_": kf, "kept_counts_": counts}
+                if polished is not None:
+                    copies["polish_counts_"] = polished
                 if self.normals:
                     # the normal pass, on the kept vertices (rows past the kept count hold no vertex: whatever comes out of them is
                     # never read) - the decoder holds the next sample's constants by now

@@ -127,6 +127,9 @@ class SampleWriter:
             if job is None:
                 rec["icp_skipped"] = True          # allow_missing_gt: no ground-truth mesh, written unaligned
         points, trans, icp_scale = mesh_utils.apply_icp(job, points)
+        if "host_polish_counts_" + part in r:          # (pipelined_two_pass(polish=True): the kept vertices are the polished ones)
+            from .project import count_record
+            rec["polish_" + part] = count_record(r["host_polish_counts_" + part].numpy())
         if self.normals:
             # (unit normals of the kept vertices: the ICP's translation and positive scale leave them as they are)
             normals = r["host_kept_normals_" + part][:len(points)].numpy()

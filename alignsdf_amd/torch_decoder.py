@@ -315,6 +315,16 @@ class TorchModuleDecoder:
             res[name] = {key: r[key] for key, keep in (("t", True), ("status", True), ("bracket", want_bracket), ("evals", want_evals)) if keep}
         return res
 
+    def project_points(self, xyz, head, max_iters=8, tol=1e-6, max_move=2.0 / 127, min_grad2=1e-12):
+        """The interface and the rule of HipSdfDecoder.project_points on the module (project.project_lockstep over this decoder's own
+        decode_points_grad): all points in lockstep under masks, one differentiated module call per step.  Covers every variant the
+        module path covers."""
+        from .project import grad_of_head, project_lockstep
+        if self._sample is None:
+            raise ValueError("no sample bound: call set_sample first")
+        xyz = xyz.detach().to(self.device, torch.float32).reshape(-1, 3).contiguous()
+        return project_lockstep(grad_of_head(self, head), xyz, max_iters, tol, max_move, min_grad2)
+
     def classify_points(self, xyz, want_sdf=True):
         if not self.num_class:
             raise ValueError("this decoder has no classifier_head (specs['ClassifierBranch'] is off)")

@@ -178,9 +178,26 @@ def _normals_callable(normals, ply_filename_out, part=None):
     return normals
 
 
+def _polish_callable(polish, ply_filename_out, part=None):
+    """The `polish` option of export_surface: a callable as it is; an evaluator with project_points -> project.VertexPolish of head
+    `part` (None: the head the file name ends in, as for the normals)."""
+    if not polish:
+        return None
+    if hasattr(polish, "project_points"):
+        from ..project import VertexPolish
+        part = part or str(ply_filename_out).split("_")[-1].split(".")[0]
+        if part not in ("hand", "obj"):
+            raise ValueError("polish on an evaluator needs normals_part=\"hand\" / \"obj\" or a file name that ends in _hand.ply / "
+                             "_obj.ply (got %r)" % (ply_filename_out,))
+        return VertexPolish(polish, part)
+    if not callable(polish):
+        raise TypeError("polish: a bound evaluator (project_points) or a callable (verts, origin, voxel_size) -> verts")
+    return polish
+
+
 def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, eval_mode=False,
                    task="obman", largest_component=True, data_root="data", kept=None, allow_missing_gt=False, normals=False,
-                   normals_part=None):
+                   normals_part=None, polish=False):
     """The host tail of convert_sdf_samples_to_ply for an already extracted surface (utils/mesh.py:360-397): place_vertices, the
     largest-component filter, in eval mode the translate+scale ICP (K7) against the ground-truth mesh, export.
     Returns (verts, faces, trans, scale).  `kept` = (verts, faces) of the largest component in lattice units when the caller has
@@ -191,14 +208,26 @@ def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename
     `normals`: the bound evaluator, or a callable that maps normalised points (device, [V, 3]) to unit normals - the file then carries
     nx / ny / nz per vertex, evaluated at origin + v * voxel_size of the written vertices (before offset, scale and ICP: a
     translation and a positive uniform scale leave a normal as it is).  An evaluator gives the normals of head `normals_part`
-    ("hand" / "obj"; by default the one the file name ends in)."""
+    ("hand" / "obj"; by default the one the file name ends in).
+    `polish`: the bound evaluator, or a callable (verts in lattice units on the device, origin, voxel_size) -> verts - the vertices
+    that are written (the kept component, or the whole surface without the filter) are moved onto the zero level of head `normals_part`
+    behind the filter and before everything else: the ICP, the normals and the file see the polished positions; faces stay."""
     normals = _normals_callable(normals, ply_filename_out, normals_part)
+    polish = _polish_callable(polish, ply_filename_out, normals_part)
     if kept is None and largest_component:
         vd = verts_d if isinstance(verts_d, torch.Tensor) else torch.as_tensor(np.asarray(verts_d))
         fd = faces_d if isinstance(faces_d, torch.Tensor) else torch.as_tensor(np.asarray(faces_d))
         kv, kf, counts = keep_largest_component_device(vd.cuda().float(), fd.cuda().int(), voxel_size, voxel_grid_origin)
         c = counts.cpu().numpy()                   # (synchronises)
         kept = kv[:c[0]], kf[:c[1]]
+    if polish is not None:
+        target = kept[0] if kept is not None else verts_d
+        target = target if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target))
+        moved = polish(target.cuda().float(), voxel_grid_origin, voxel_size)
+        if kept is not None:
+            kept = moved, kept[1]
+        else:
+            verts_d = moved
     verts, faces, out_v = place_vertices(verts_d, faces_d, voxel_grid_origin, voxel_size, offset, scale)
     out_f = faces
     if kept is not None:
@@ -229,13 +258,13 @@ def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename
 
 def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_size, ply_filename_out, offset=None,
                                scale=None, eval_mode=False, task="obman", largest_component=True, data_root="data",
-                               allow_missing_gt=False, normals=False, normals_part=None):
+                               allow_missing_gt=False, normals=False, normals_part=None, polish=False):
     """Iso-surface of one SDF volume -> .ply (utils/mesh.py:331-399).  Returns (verts, faces, trans, scale) with
     verts / faces the raw marching-cubes output like the reference.  MC failures are logged and skipped exactly
     like the reference (utils/mesh.py:353-358).  The written file holds the largest watertight component when the
     surface splits into several (utils/mesh.py:371-381, K8 / alignsdf_amd.mesh_post); in eval mode it is first aligned to
     the ground-truth mesh by the translate+scale ICP (utils/mesh.py:385-395, alignsdf_amd.icp) and `trans`, `scale`
-    are the ICP's; otherwise they are zeros / one.  `normals`, `normals_part`: see export_surface."""
+    are the ICP's; otherwise they are zeros / one.  `normals`, `normals_part`, `polish`: see export_surface."""
     vol = pytorch_3d_sdf_tensor if isinstance(pytorch_3d_sdf_tensor, torch.Tensor) else torch.as_tensor(np.asarray(pytorch_3d_sdf_tensor))
     if not vol.is_cuda:
         vol = vol.cuda()
@@ -246,7 +275,8 @@ def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_s
         print(e)
         return None, None, np.array([0, 0, 0]), np.array([1])
     return export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset, scale, eval_mode, task,
-                          largest_component, data_root, allow_missing_gt=allow_missing_gt, normals=normals, normals_part=normals_part)
+                          largest_component, data_root, allow_missing_gt=allow_missing_gt, normals=normals, normals_part=normals_part,
+                          polish=polish)
 
 
 # colour per part label of the `--viz` output (the table of utils/mesh.py:305-310)
@@ -329,26 +359,33 @@ def decode_two_pass(hand_branch, obj_branch, decoder, latent_vec, mano_results, 
 
 
 def write_hand_and_object(r, filename, hand_branch, obj_branch, offset=None, scale=None, eval_mode=False, task="obman", after_hand=None,
-                          normals=None):
+                          normals=None, polish=None):
     """<filename>_hand.ply, then <filename>_obj.ply, from the volumes of decode_two_pass.  As in the reference, the object mesh is
     written with the hand mesh's ICP translation / scale as its offset / scale (utils/mesh.py:123-133,186-195); the caller's
     `offset` / `scale` reach it only when the hand branch is off.  `after_hand(verts, faces, offset, scale, stats)` runs between the
     two files when the hand has a surface.  `normals`: the evaluator, still bound to this sample - the files then carry vertex normals
-    and the stats their `normals_degenerate_<part>` counts.  Returns the per-surface (V, F) counts."""
+    and the stats their `normals_degenerate_<part>` counts.  `polish`: the same evaluator - the written vertices are moved onto the
+    zero level of their own head first (export_surface) and the stats carry `polish_<part>` (project.count_record).  Returns the
+    per-surface (V, F) counts."""
     stats = {}
+    pol = {part: _polish_callable(polish, "", part) or False for part in ("hand", "obj")}
     fn = {part: VertexNormals(normals, part) if normals is not None else False for part in ("hand", "obj")}
     if hand_branch:
         v, f, offset, scale = convert_sdf_samples_to_ply(r["vol_hand"], r["origin"], r["voxel_size"], filename + "_hand.ply", None,
-                                                         None, eval_mode, task, normals=fn["hand"])
+                                                         None, eval_mode, task, normals=fn["hand"], polish=pol["hand"])
         stats["hand"] = (0, 0) if v is None else (len(v), len(f))
+        if polish is not None and v is not None:
+            stats["polish_hand"] = pol["hand"].counts
         if normals is not None and v is not None:
             stats["normals_degenerate_hand"] = fn["hand"].degenerate
         if after_hand is not None and v is not None:
             after_hand(v, f, offset, scale, stats)
     if obj_branch:
         v, f, _, _ = convert_sdf_samples_to_ply(r["vol_obj"], r["origin"], r["voxel_size"], filename + "_obj.ply", offset, scale,
-                                                False, normals=fn["obj"])
+                                                False, normals=fn["obj"], polish=pol["obj"])
         stats["obj"] = (0, 0) if v is None else (len(v), len(f))
+        if polish is not None and v is not None:
+            stats["polish_obj"] = pol["obj"].counts
         if normals is not None and v is not None:
             stats["normals_degenerate_obj"] = fn["obj"].degenerate
     return stats
@@ -357,7 +394,7 @@ def write_hand_and_object(r, filename, hand_branch, obj_branch, offset=None, sca
 def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, latent_vec, mano_results, obj_results, cam_intr,
                                  specs, filename, N=256, max_batch=32 ** 3, offset=None, scale=None, device="cpu",
                                  label_out=False, viz=False, eval_mode=False, task="obman", grid_mode="reference", return_stats=False,
-                                 normals=False):
+                                 normals=False, polish=False):
     """Hand + object meshes of one sample (utils/mesh.py:17-195): writes <filename>_hand.ply / _obj.ply.
     `max_batch` and `device` are accepted for signature compatibility; chunking is internal to the kernel and
     the decoder's device is used.  `grid_mode="reference"` reproduces the true-division lattice of
@@ -370,12 +407,19 @@ def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, l
     written with the hand mesh's ICP translation / scale as its offset / scale (utils/mesh.py:123-133,186-195).
     `normals=True`: both files carry per-vertex unit normals (nx / ny / nz) - the analytic SDF gradient of the surface's own head at
     the vertex, normalised - and the stats dict their `normals_degenerate_hand` / `_obj` counts; a decoder the gradient kernel does
-    not cover raises NotImplementedError before anything is swept."""
+    not cover raises NotImplementedError before anything is swept.
+    `polish=True`: the written vertices of both files are moved onto the zero level of their surface's own head (Newton projection,
+    at most one fine voxel per axis: project.polish_vertices) - same faces and vertex count, normals taken at the polished positions,
+    `polish_hand` / `polish_obj` in the stats; an evaluator that cannot project raises NotImplementedError before anything is swept."""
     decoder.eval() if hasattr(decoder, "eval") else None
     evaluator = None
-    if normals:
+    if normals or polish:
         evaluator = decoder_for(decoder, specs, mano_results)
+    if normals:
         require_normals(evaluator)
+    if polish:
+        from ..project import require_polish
+        require_polish(evaluator)
     # (the volumes go to marching cubes only: a decoder set to the narrow-band fine sweep may use it)
     r = decode_two_pass(hand_branch, obj_branch, decoder, latent_vec, mano_results, obj_results, specs, N, grid_mode, cam_intr,
                         mc_only=True)
@@ -390,5 +434,5 @@ def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, l
         stats["labels"] = labels
 
     stats = write_hand_and_object(r, filename, hand_branch, obj_branch, offset, scale, eval_mode, task, label_pass if label_out else None,
-                                  normals=evaluator)
+                                  normals=evaluator if normals else None, polish=evaluator if polish else None)
     return stats if return_stats else None

@@ -27,6 +27,7 @@ extern "C" {
 #define ASDF_ENOSURF (-7)    /* no surface found (skimage RuntimeError) */
 #define ASDF_ENOGRAD (-8)    /* asdf_decode_points_grad: a decoder / sample its kernel is not built for */
 #define ASDF_ENOTRACE (-9)   /* asdf_trace_rays: a decoder / sample its kernel is not built for */
+#define ASDF_ENOPROJECT (-10) /* asdf_project_points: a decoder / sample its kernel is not built for */
 
 #define ASDF_MAX_HEADS 2
 #define ASDF_MAX_POINT_FEATS 64
@@ -312,6 +313,40 @@ typedef struct asdf_trace_params {
 int asdf_trace_rays(asdf_decoder_t* dec, const float* rays_dev, int64_t M, const asdf_trace_params_t* params,
                     float* t_hand_dev, int32_t* status_hand_dev, float* bracket_hand_dev, int32_t* evals_hand_dev,
                     float* t_obj_dev, int32_t* status_obj_dev, float* bracket_obj_dev, int32_t* evals_obj_dev, void* stream);
+
+/* Newton projection onto the zero level: M points xyz_dev [M][3] are moved onto the surface of ONE head (0 = hand, 1 = object) inside
+ * one kernel (csrc/k1p_kernels.hip - a point occupies the four columns of asdf_decode_points_grad, and a workgroup sends its 32 points
+ * through the head's weight stream again while one of them is live).  No counterpart in the reference (its vertices stay where the
+ * linear interpolation of marching cubes puts them).  The rule, per point, all in fp32 with every operation rounded on its own and no
+ * fused multiply-add outside the MLP:
+ *   start     x0 (the input position) not finite: ASDF_PROJECT_BAD, 0 evaluations; the outputs are x0 and zeros.  Else x = x0.
+ *   evaluate  f = the head's sdf at x (asdf_decode_points' bits under ASDF_MATH_F32), g = its gradient (asdf_decode_points_grad's
+ *             bits).  The first f is sdf_in.
+ *   decide    in this order:  |f| <= tol -> CONVERGED;  n2 = (g0 g0 + g1 g1) + g2 g2, !(n2 >= min_grad2) -> STALLED (a NaN lands
+ *             here);  max_iters steps already taken -> SPENT.
+ *   step      s = f / n2 (correctly rounded division); per axis k: x_k = clamp(x_k - s g_k, x0_k - max_move, x0_k + max_move), the
+ *             clamp written with comparisons (v > lo ? v : lo, then v < hi ? v : hi); evaluate again.
+ * Outputs, each may be NULL: xyz_out [M][3] the LAST iterate (not the best: where |sdf| > |sdf_in| the caller keeps its input), sdf [M]
+ * and grad [M][3] at xyz_out (so normals come with it), sdf_in [M], status [M] (ASDF_PROJECT_*), evals [M] = decoder evaluations the
+ * point took (<= max_iters + 1).  xyz_out may be xyz_dev itself (a point is read once, before it is written).  The call always runs on
+ * the fp32 chain and neither reads nor changes the decoder's math mode or MFMA shape; it uses no scratch of the decoder.  M == 0 is
+ * ASDF_OK and launches nothing.
+ * ASDF_EINVAL: NULL decoder, no sample bound, M < 0, NULL xyz, NULL params, a head the decoder lacks, max_iters < 0, tol < 0 (or NaN),
+ * max_move or min_grad2 not > 0.  ASDF_ENOPROJECT: CombinedDecoder, NeRF-encoded point features, a pixel-aligned sample (exactly what
+ * asdf_decode_points_grad answers with ASDF_ENOGRAD). */
+#define ASDF_PROJECT_CONVERGED 0
+#define ASDF_PROJECT_SPENT 1
+#define ASDF_PROJECT_STALLED 2
+#define ASDF_PROJECT_BAD 3
+typedef struct asdf_project_params {
+  int32_t max_iters;    /* steps a point may take (>= 0) */
+  float tol;            /* a point is done when |f| <= tol (>= 0) */
+  float max_move;       /* per-axis trust box around the input position (> 0) */
+  float min_grad2;      /* smallest squared gradient norm that may be divided by (> 0) */
+} asdf_project_params_t;
+int asdf_project_points(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, int32_t head, const asdf_project_params_t* params,
+                        float* xyz_out_dev, float* sdf_dev, float* grad_dev, float* sdf_in_dev, int32_t* status_dev, int32_t* evals_dev,
+                        void* stream);
 
 /* ---- Arithmetic of the three hidden GEMMs of the grid sweeps (asdf_decode_grid; explicit point lists always run
  * ASDF_MATH_F32 - they have no bbox record to carry the range report below):
