@@ -35,7 +35,7 @@ EXPORTS = (
     "asdf_sample_surface_workspace_bytes", "asdf_sample_surface", "asdf_icp_normalise",
     "asdf_decoder_set_sample_host", "asdf_decoder_set_cluster_timeout", "asdf_set_mfma_shape", "asdf_get_mfma_shape",
     "asdf_debug_pack_host_f16w", "asdf_decoder_set_sample_pixel", "asdf_decode_points_grad", "asdf_trace_rays",
-    "asdf_project_points",
+    "asdf_project_points", "asdf_interaction_lattice", "asdf_interaction_points",
 )
 MATH_F32, MATH_F16X3 = 0, 1
 MAX_CLASSES = 8
@@ -51,6 +51,9 @@ REC_AUDIT_MAX_ERR, REC_AUDIT_FLIPS, REC_AUDIT_EVALS, REC_NEAR_OVERFLOW = 35, 36,
 REC_SHELL_PICKS, REC_SHELL_POPULATION, REC_AUDIT_SUMSQ, REC_WORDS = 39, 40, 41, 48
 NEAR_CAP, CAND_CAP, BAND_CAP = 1 << 16, 1 << 21, 1 << 22
 BOX_RANGE_WORDS = (BOX_RANGE, BOX_STRIDE + BOX_RANGE)      # the range words of the hand / object head in a box record
+# The records of csrc/interaction.hip: ASDF_OVERLAP_* / ASDF_CONTACT_* under the same names without the prefix
+OVERLAP_HAND, OVERLAP_OBJ, OVERLAP_BOTH, OVERLAP_NAN, OVERLAP_MIN, OVERLAP_MAX, OVERLAP_WORDS = 0, 1, 2, 3, 4, 7, 16
+CONTACT_COUNT, CONTACT_INSIDE, CONTACT_NEAR, CONTACT_NAN, CONTACT_MIN_BITS, CONTACT_ARGMIN, CONTACT_WORDS = 0, 1, 2, 3, 4, 5, 8
 
 
 def box_of(rec, head):
@@ -141,6 +144,8 @@ def lib():
     L.asdf_decoder_set_classifier.argtypes = [vp, vp, vp, i32]
     L.asdf_decode_points_cls.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     L.asdf_neg_bbox.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.asdf_interaction_lattice.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    L.asdf_interaction_points.argtypes = [vp, i32, vp, f32, vp, vp]
     L.asdf_mc_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.asdf_mc_count.argtypes = [vp, i32, i32, i32, ctypes.c_double, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
                                 ctypes.POINTER(ctypes.c_uint32), vp]

@@ -497,6 +497,7 @@ def main(argv=None):
     rc.add_normals_argument(p)      # --normals: per-vertex unit normals in every file
     rc.add_polish_argument(p)       # --polish: the vertices of every file moved onto the zero level of the SDF
     rc.add_render_arguments(p)      # --render HxW [--cameras DIR]: one ray-cast view per sample
+    rc.add_interaction_arguments(p)  # --interaction [--contact_mm MM]: penetration depth, intersection volume, contact per sample
     args = p.parse_args(argv)
     render = rc.render_from_args(args, p)
     rc.apply_sweep_arguments(args)
@@ -512,6 +513,11 @@ def main(argv=None):
         ranges = [tuple(s["range"]) for s in shards]
         summary = rc.merge_sweeps_json(output_dir, ranges=ranges)
         print(rc.sweeps_summary_line(json.load(open(summary))["totals"]) + " (%s)" % summary)
+        if args.interaction or args.merge_only is not None:
+            # interaction.json / interaction.txt from the ranks' interaction_<start>_<end>.json (--merge-only: where a run left them)
+            merged_path = rc.merge_interaction_json(output_dir, ranges=ranges)
+            if merged_path is not None:
+                print(rc.interaction_summary_line(json.load(open(merged_path))["summary"]) + " (%s)" % merged_path)
         print("reconstructed %d samples" % len(records))
         skipped = sum(1 for r in records if r.get("icp_skipped"))
         if skipped:
@@ -535,7 +541,8 @@ def main(argv=None):
             recs = rc.reconstruct(decoder, specs, split, output_dir, start, end, task=args.task, cube_dim=args.cube_dim,
                                   eval_mode=True, label_out=args.optim, code_source=source, data_root=args.data_root,
                                   allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None, stride=stride,
-                                  on_record=progress, normals=args.normals, **({"polish": True} if args.polish else {}), **render)
+                                  on_record=progress, normals=args.normals, **({"polish": True} if args.polish else {}), **render,
+                                  **rc.interaction_from_args(args))
         except Exception as e:
             for r in getattr(e, "partial_records", []) or []:
                 r["milliseconds"] = 1e3 * r.get("seconds", 0.0)

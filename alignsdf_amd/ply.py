@@ -4,8 +4,9 @@ deep_sdf/mesh.py:107-112)."""
 import numpy as np
 
 
-def write_ply(path, verts, faces, normals=None):
-    """normals [V, 3] (optional): written as `property float nx / ny / nz` behind z; without them the file is the layout above."""
+def write_ply(path, verts, faces, normals=None, quality=None):
+    """normals [V, 3] (optional): written as `property float nx / ny / nz` behind z; quality [V] (optional): one more float per vertex,
+    `property float quality`, behind z / nz (the name mesh viewers colour by); without them the file is the layout above."""
     verts = np.ascontiguousarray(verts, dtype="<f4").reshape(-1, 3)
     faces = np.ascontiguousarray(faces, dtype="<i4").reshape(-1, 3)
     props = "property float x\nproperty float y\nproperty float z\n"
@@ -15,6 +16,12 @@ def write_ply(path, verts, faces, normals=None):
             raise ValueError("%d normals for %d vertices" % (len(normals), len(verts)))
         props += "property float nx\nproperty float ny\nproperty float nz\n"
         verts = np.ascontiguousarray(np.hstack([verts, normals]))
+    if quality is not None:
+        quality = np.ascontiguousarray(quality, dtype="<f4").reshape(-1, 1)
+        if len(quality) != len(verts):
+            raise ValueError("%d quality values for %d vertices" % (len(quality), len(verts)))
+        props += "property float quality\n"
+        verts = np.ascontiguousarray(np.hstack([verts, quality]))
     header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%selement face %d\nproperty list uchar int vertex_indices\n"
               "end_header\n" % (len(verts), props, len(faces)))
     rec = np.empty(len(faces), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
@@ -31,9 +38,10 @@ _PLY_SCALARS = {"char": "i1", "uchar": "u1", "short": "<i2", "ushort": "<u2", "i
                 "float64": "<f8"}
 
 
-def read_ply(path, with_normals=False):
-    """Inverse of write_ply: (verts, faces), or (verts, faces, normals or None) with with_normals=True.  The vertex record is
-    taken from the header's scalar properties, so files with normals (or other per-vertex scalars) read correctly."""
+def read_ply(path, with_normals=False, with_quality=False):
+    """Inverse of write_ply: (verts, faces), or (verts, faces, normals or None) with with_normals=True; with_quality=True appends
+    the `quality` column (or None) to either.  The vertex record is taken from the header's scalar properties, so files with normals
+    (or other per-vertex scalars) read correctly."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -54,11 +62,13 @@ def read_ply(path, with_normals=False):
     vrec = np.frombuffer(data, dtype=np.dtype(fields), count=nv, offset=end)
     verts = np.stack([vrec[k] for k in ("x", "y", "z")], 1).astype(np.float32)
     rec = np.frombuffer(data, dtype=[("n", "u1"), ("idx", "<i4", (3,))], count=nf, offset=end + nv * vrec.dtype.itemsize)
-    if not with_normals:
-        return verts, rec["idx"].copy()
     names = vrec.dtype.names
-    normals = np.stack([vrec[k] for k in ("nx", "ny", "nz")], 1).astype(np.float32) if all(k in names for k in ("nx", "ny", "nz")) else None
-    return verts, rec["idx"].copy(), normals
+    out = (verts, rec["idx"].copy())
+    if with_normals:
+        out += (np.stack([vrec[k] for k in ("nx", "ny", "nz")], 1).astype(np.float32) if all(k in names for k in ("nx", "ny", "nz")) else None,)
+    if with_quality:
+        out += (vrec["quality"].astype(np.float32) if "quality" in names else None,)
+    return out
 
 
 def write_ply_ascii(path, verts, faces=None, vertex_colors=None):

@@ -19,6 +19,8 @@ import torch
 # (tests, tools, bench.py, dist_reconstruct and the docs reach the helpers below through this module)
 from .code_sources import CodeUploader, code_source_from_args, npz_code_source, synthetic_code_source  # noqa: F401
 from .gt_prefetch import GroundTruthPrefetcher  # noqa: F401
+from .interaction import (add_interaction_arguments, interaction_from_args, merge_interaction_json,  # noqa: F401
+                          summarise as summarise_interaction, summary_line as interaction_summary_line)
 from .networks.model import build_decoder
 from .sample_pipeline import pipelined_two_pass
 from .sample_writer import FileWriter, SampleWriter  # noqa: F401
@@ -58,7 +60,7 @@ def reconstruct_sample(decoder, specs, latent, mano_results, obj_results, N, mes
 def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, end_point, task="obman", device="cuda", scale=None,
                 cube_dim=128, label_out=False, viz=False, eval_mode=False, code_source=None, grid_mode="reference",
                 data_root="data", allow_missing_gt=False, fast=None, stride=1, on_record=None, normals=False, render=None,
-                camera_source=None, polish=False):
+                camera_source=None, polish=False, interaction=None):
     """Reconstruct samples [start_point, end_point) of a split file (reconstruct.py:33-95).  `loaded_model` is the
     decoder module, or any wrapper exposing it as `.module.decoder` / `.decoder` like the reference's DataParallel model.
     `fast`: see pipelined_two_pass (default: ordinary sweeps, every voxel at <= 1e-5).  `stride` > 1: every stride-th sample of the
@@ -76,6 +78,11 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
     `polish_hand` / `polish_obj` = {"converged", "spent", "stalled", "bad", "kept"}: vertices by status of the projection, and how many
     stayed at their marching-cubes position; an evaluator that cannot project raises NotImplementedError before the first sweep and
     before any file is written.
+    `interaction={"contact_m": 0.005}`: how the hand and the object relate, from the decoder's own two SDFs (interaction.py; see
+    pipelined_two_pass) - every record gains `interaction` (penetration depth, intersection volume, contact, ...: interaction_record),
+    every mesh file `property float quality` = the signed distance in metres to the other surface at the vertex, and the output
+    directory interaction_<start>_<end>.json, interaction.json and interaction.txt.  Taken in the decoder's own frame, before the
+    eval-mode ICP.  ValueError before the first sweep when a branch is off.
     Returns the list of per-sample records."""
     if render is not None and camera_source is None:
         raise ValueError("reconstruct(render=...) needs a camera_source: render.npz_camera_source(<dir of <sample>.npz with cam_intr and "
@@ -91,8 +98,12 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
         # synthetic latents here, which wrote meaningless <real sample>_hand.ply files that the evaluation then scored.)
         raise ValueError("reconstruct() needs a code_source: npz_code_source(<dir of per-sample .npz codes>), "
                          "model_output_code_source(<encoder callable>), or synthetic_code_source(...) for tests and benchmarks")
+    measure = {}
+    if interaction is not None and interaction is not False:
+        from .interaction import check_option
+        measure = {"interaction": {"contact_m": check_option(interaction, specs), "scale_factor": specs["SdfScaleFactor"]}}
     out = SampleWriter(output_dir, (start_point, end_point, stride), cube_dim, specs.get("HandBranch", True), scale, viz,
-                       (task, data_root, allow_missing_gt) if eval_mode else None, normals=normals)
+                       (task, data_root, allow_missing_gt) if eval_mode else None, normals=normals, **measure)
 
     def samples():
         for k, path in enumerate(names):
@@ -103,6 +114,8 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
     extra = {"normals": True} if normals else {}          # (the option travels only when it is on)
     if polish:
         extra["polish"] = True
+    if measure:
+        extra["interaction"] = {"contact_m": measure["interaction"]["contact_m"]}
     if render is not None:
         from .render import trace_defaults
         extra["render"] = {"size": (int(render[0]), int(render[1])), "camera": lambda key: camera_source(key[1], key[0]),
@@ -122,6 +135,10 @@ def reconstruct(loaded_model, specs, split_filename, output_dir, start_point, en
         out.close(failing=True)
         raise
     out.close()
+    if measure:
+        # this range's interaction.json / interaction.txt (a sharded run merges every rank's range over them at its end)
+        from .interaction import merge_interaction_json
+        merge_interaction_json(output_dir, ranges=[(start_point, end_point)])
     return out.records
 
 
@@ -215,6 +232,7 @@ def main(argv=None):
     add_normals_argument(p)
     add_polish_argument(p)
     add_render_arguments(p)
+    add_interaction_arguments(p)
     args = p.parse_args(argv)
     render = render_from_args(args, p)
     apply_sweep_arguments(args)
@@ -226,10 +244,13 @@ def main(argv=None):
         with open(split) as f:
             args.start_point, args.end_point = 0, len(json.load(f)["filenames"])
     source = code_source_from_args(args, specs, p)
-    return reconstruct(decoder, specs, split, output_dir, args.start_point, args.end_point, task=args.task, cube_dim=args.cube_dim,
-                       label_out=args.label_out, viz=args.viz, eval_mode=args.eval_mode, code_source=source,
-                       allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None, normals=args.normals,
-                       **({"polish": True} if args.polish else {}), **render)
+    records = reconstruct(decoder, specs, split, output_dir, args.start_point, args.end_point, task=args.task, cube_dim=args.cube_dim,
+                          label_out=args.label_out, viz=args.viz, eval_mode=args.eval_mode, code_source=source,
+                          allow_missing_gt=args.allow_missing_gt, fast=True if args.fast else None, normals=args.normals,
+                          **({"polish": True} if args.polish else {}), **render, **interaction_from_args(args))
+    if args.interaction:
+        print(interaction_summary_line(summarise_interaction(records)))
+    return records
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ from .utils import mesh as mesh_utils, utils
 
 
 def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_copy=False, label_out=False, midpoint=None, report=None,
-                       fast=None, normals=False, render=None, polish=False):
+                       fast=None, normals=False, render=None, polish=False, interaction=None):
     """Software pipeline over independent samples.  `samples` yields (key, latent, mano_results, obj_results); the
     generator yields (key, result) in order, where result holds the pass-2 volumes (device), the zoom cube and the
     marching-cubes output per enabled branch (`verts_*`, `faces_*` device tensors, absent when MC found no surface).
@@ -58,8 +58,17 @@ def pipelined_two_pass(decoder, specs, samples, N, grid_mode="reference", host_c
     status and of vertices kept in place: `polish_counts_*` on the device, `host_polish_counts_*` with the other copies.  The sample
     is re-bound first, as for the normal pass.  A decoder that cannot project raises NotImplementedError before the first sweep.
 
+    interaction={"contact_m": 0.005} (with host_copy; None = off) runs the interaction pass (interaction.interaction_pass) inside
+    post-processing - the fine pass is accepted by then and `vol_*` are final -, behind K8 and the polish pass of BOTH surfaces and
+    before the normal pass and the host copies: the overlap of the two fine volumes by sign, and per surface the OTHER head's SDF at its
+    kept (polished) vertices, reduced on the device with K8's kept count read there.  `interaction` in the result (device: "words",
+    "other_sdf_<part>"), `host_interaction` (int32 [interaction.WORDS]) and `host_other_sdf_<part>` at input capacity behind
+    `copy_done_interaction`, and `interaction_contact_m`.  In the decoder's own frame, before the eval-mode hook.  The sample is re-bound
+    first, as for the normal pass.  ValueError before the first sweep when a branch is off, or without host_copy.
+
     report, if given (a dict), receives the evaluator that ran and a snapshot of its sweep counters (see write_sweeps_json)."""
-    yield from SamplePipeline(decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals, render, polish).run()
+    yield from SamplePipeline(decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals, render, polish,
+                              interaction).run()
 
 
 @dataclasses.dataclass(slots=True, eq=False)
@@ -77,9 +86,17 @@ class InFlight:
 class SamplePipeline:
     """pipelined_two_pass: the decoder and the state its stages share, one method per stage, and the window over the samples (run)."""
 
-    def __init__(self, decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals=False, render=None, polish=False):
+    def __init__(self, decoder, specs, samples, N, grid_mode, host_copy, label_out, midpoint, report, fast, normals=False, render=None, polish=False,
+                 interaction=None):
         self.specs, self.N, self.host_copy, self.label_out, self.midpoint = specs, N, host_copy, label_out, midpoint
         self.normals, self.render, self.polish = bool(normals), render, bool(polish)
+        self.contact_m = None                      # the contact distance of the interaction pass; None = the pass is off
+        if interaction is not None and interaction is not False:
+            from .interaction import check_option
+            self.contact_m = check_option(interaction, specs)      # (before the first sweep: both branches are needed)
+            if not host_copy:
+                # (the pass measures K8's kept vertices, which exist with host_copy only: no run that quietly reports nothing)
+                raise ValueError("interaction needs host_copy=True: it measures the kept vertices of the component filter")
         self.samples = (InFlight(key, codes) for key, *codes in samples)   # (lazy: a sample is fetched when the window asks for it)
         self.head = next(self.samples, None)
         if self.head is None:                      # (an empty stream: no decoder is asked for)
@@ -228,7 +245,9 @@ class SamplePipeline:
                     r["copy_done_render"] = self.to_host(r, "render_" + name, t)
 
     def post_process_surfaces(self, s, r):
-        """The per-surface part of post_process."""
+        """The per-surface part of post_process; with the interaction pass, K8 and the polish pass of both surfaces come first, then
+        that pass, then what is left per surface (copy_surface)."""
+        finish = []          # with the interaction pass: what follows it per surface (normal pass, host copies)
         for _, part in self.parts:
             if "verts_" + part not in r:
                 continue
@@ -253,21 +272,41 @@ class SamplePipeline:
                     kv, polished = polish_vertices(self.hip, kv, r["origin"], r["voxel_size"], part, count=counts[0])
                     r["polish_counts_" + part] = polished
                 r["kept_dev_" + part] = (kv, kf, counts)       # (the eval-mode hook samples the kept surface on the device)
-                copies = {"kept_verts_": kv, "kept_faces_": kf, "kept_counts_": counts}
-                if polished is not None:
-                    copies["polish_counts_"] = polished
-                if self.normals:
-                    # the normal pass, on the kept vertices (rows past the kept count hold no vertex: whatever comes out of them is
-                    # never read) - the decoder holds the next sample's constants by now
-                    if self.bound is not s:
-                        self.bind(s)
-                    res = self.hip.decode_points_grad(mesh_utils.lattice_points(kv, r["origin"], r["voxel_size"]), hand=part == "hand",
-                                                      obj=part == "obj")
-                    r["kept_normals_" + part] = copies["kept_normals_"] = mesh_utils.unit_normals(res[1] if part == "hand" else res[3])
-                if "labels_" + part in r:
-                    copies.update({"verts_": v, "faces_": f, "labels_": r["labels_" + part]})
-                for name, t in copies.items():
-                    r["copy_done_" + part] = self.to_host(r, name + part, t)       # the side stream is in order: the last event covers all
+                if self.contact_m is None:
+                    self.copy_surface(s, r, part, v, f, polished)
+                else:
+                    finish.append((part, v, f, polished))
+        if self.contact_m is not None:
+            # the interaction pass, once both surfaces have their kept (polished) vertices and before anything of them is copied - the
+            # decoder holds the next sample's constants by now
+            from .interaction import interaction_pass
+            if self.bound is not s:
+                self.bind(s)
+            r["interaction"] = res = interaction_pass(self.hip, r, self.specs, self.contact_m)
+            r["interaction_contact_m"] = self.contact_m
+            for args in finish:
+                self.copy_surface(s, r, *args)
+            for name, t in res.items():
+                r["copy_done_interaction"] = self.to_host(r, "interaction" if name == "words" else name, t)
+
+    def copy_surface(self, s, r, part, v, f, polished):
+        """Normal pass and host copies of one surface behind K8 (and the polish pass)."""
+        kv, kf, counts = r["kept_dev_" + part]
+        copies = {"kept_verts_": kv, "kept_faces_": kf, "kept_counts_": counts}
+        if polished is not None:
+            copies["polish_counts_"] = polished
+        if self.normals:
+            # the normal pass, on the kept vertices (rows past the kept count hold no vertex: whatever comes out of them is
+            # never read) - the decoder holds the next sample's constants by now
+            if self.bound is not s:
+                self.bind(s)
+            res = self.hip.decode_points_grad(mesh_utils.lattice_points(kv, r["origin"], r["voxel_size"]), hand=part == "hand",
+                                              obj=part == "obj")
+            r["kept_normals_" + part] = copies["kept_normals_"] = mesh_utils.unit_normals(res[1] if part == "hand" else res[3])
+        if "labels_" + part in r:
+            copies.update({"verts_": v, "faces_": f, "labels_": r["labels_" + part]})
+        for name, t in copies.items():
+            r["copy_done_" + part] = self.to_host(r, name + part, t)       # the side stream is in order: the last event covers all
 
     def run(self):
         """The window: sample k (`cur`) is finished while k+1 (`nxt`) is in the queue and k+2 (`after`) is fetched and enqueued."""

@@ -41,11 +41,12 @@ class FileWriter:
         if first is not None:
             raise first
 
-    def write_ply(self, path, verts, faces, normals=None):
+    def write_ply(self, path, verts, faces, normals=None, quality=None):
         from .ply import write_ply
         self.poll()
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        self.jobs.append((path, self.pool.submit(write_ply, path, verts, faces, normals)))
+        extra = () if quality is None else (quality,)          # (the option travels only when it is on)
+        self.jobs.append((path, self.pool.submit(write_ply, path, verts, faces, normals, *extra)))
 
     def write_view(self, path, view, H, W, trace):
         from .render import save_view
@@ -75,11 +76,14 @@ class SampleWriter:
     its ground truth in eval mode, the object under the hand's transform), the label files follow, and a record says what was written.
     close() ends the helpers and leaves the shard's sweeps report next to meshes/."""
 
-    def __init__(self, output_dir, shard, cube_dim, hand_on, scale=None, viz=False, ground_truth=None, normals=False):
+    def __init__(self, output_dir, shard, cube_dim, hand_on, scale=None, viz=False, ground_truth=None, normals=False, interaction=None):
         """`shard` = (start_point, end_point, stride), for the sweeps report; `ground_truth` = (task, data_root, allow_missing_gt) in
         eval mode - the hand is what gets aligned, so without a hand branch there is no prefetcher.  `normals`: the results carry
-        `host_kept_normals_*` (pipelined_two_pass(normals=True)) and every file is written with them."""
+        `host_kept_normals_*` (pipelined_two_pass(normals=True)) and every file is written with them.  `interaction` =
+        {"contact_m", "scale_factor"}: the results carry `host_interaction` (pipelined_two_pass(interaction=...)) - every record gains
+        `interaction`, every file `quality`, and close() leaves the shard's interaction_<start>_<end>.json next to the sweeps report."""
         self.output_dir, self.shard, self.cube_dim, self.normals = output_dir, shard, cube_dim, bool(normals)
+        self.interaction = interaction
         self.mesh_dir = os.path.join(output_dir, "meshes")
         os.makedirs(self.mesh_dir, exist_ok=True)
         self.hand_on, self.scale, self.viz = hand_on, scale, viz
@@ -130,10 +134,18 @@ class SampleWriter:
         if "host_polish_counts_" + part in r:          # (pipelined_two_pass(polish=True): the kept vertices are the polished ones)
             from .project import count_record
             rec["polish_" + part] = count_record(r["host_polish_counts_" + part].numpy())
+        normals = None
         if self.normals:
             # (unit normals of the kept vertices: the ICP's translation and positive scale leave them as they are)
             normals = r["host_kept_normals_" + part][:len(points)].numpy()
             rec["normals_degenerate_" + part] = mesh_utils.count_degenerate(normals)
+        if self.interaction is not None:
+            # quality: the signed distance in metres to the OTHER surface, by the other head's SDF at this vertex - in the decoder's
+            # frame (the eval-mode ICP moves the positions, not these values)
+            r["copy_done_interaction"].synchronize()
+            quality = r["host_other_sdf_" + part][:len(points)].numpy() * np.float32(2.0 / self.interaction["scale_factor"])
+            self.writer.write_ply(base + ".ply", points, faces, normals, quality)
+        elif normals is not None:
             self.writer.write_ply(base + ".ply", points, faces, normals)
         else:
             self.writer.write_ply(base + ".ply", points, faces)
@@ -178,6 +190,11 @@ class SampleWriter:
                     self.write_labels(base, r, rec, offset, sc)
         if "render" in r:
             self.write_render(self.path(name, "render") + ".npz", r, rec)
+        if self.interaction is not None and "host_interaction" in r:
+            from .interaction import PARTS, interaction_record, split_words
+            r["copy_done_interaction"].synchronize()
+            words = split_words(r["host_interaction"].numpy(), [part for part in PARTS if "verts_" + part in r])
+            rec["interaction"] = interaction_record(words, rec["voxel_size"], self.interaction["scale_factor"], self.interaction["contact_m"])
         now = time.perf_counter()
         rec["seconds"], self.t_prev = now - self.t_prev, now
         self.records.append(rec)
@@ -187,6 +204,10 @@ class SampleWriter:
         if self.sweeps:
             start, end, stride = self.shard
             write_sweeps_json(self.output_dir, start, end, self.sweeps, len(self.records), self.cube_dim, self.components, stride)
+        if self.interaction is not None:
+            from .interaction import write_interaction_json
+            start, end, stride = self.shard
+            write_interaction_json(self.output_dir, start, end, self.records, self.interaction["contact_m"], stride)
 
     def close(self, failing=False):
         """End the helpers and write the shard's sweeps report.  failing=True, while another exception unwinds: what they still have to

@@ -197,7 +197,7 @@ def _polish_callable(polish, ply_filename_out, part=None):
 
 def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, eval_mode=False,
                    task="obman", largest_component=True, data_root="data", kept=None, allow_missing_gt=False, normals=False,
-                   normals_part=None, polish=False):
+                   normals_part=None, polish=False, kept_out=None):
     """The host tail of convert_sdf_samples_to_ply for an already extracted surface (utils/mesh.py:360-397): place_vertices, the
     largest-component filter, in eval mode the translate+scale ICP (K7) against the ground-truth mesh, export.
     Returns (verts, faces, trans, scale).  `kept` = (verts, faces) of the largest component in lattice units when the caller has
@@ -211,9 +211,12 @@ def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename
     ("hand" / "obj"; by default the one the file name ends in).
     `polish`: the bound evaluator, or a callable (verts in lattice units on the device, origin, voxel_size) -> verts - the vertices
     that are written (the kept component, or the whole surface without the filter) are moved onto the zero level of head `normals_part`
-    behind the filter and before everything else: the ICP, the normals and the file see the polished positions; faces stay."""
+    behind the filter and before everything else: the ICP, the normals and the file see the polished positions; faces stay.
+    `kept_out` (a dict, optional) receives under "kept" the written surface as it stands on the device, in lattice units: (verts, faces,
+    counts) - the kept component, polished where that is on; counts = K8's int32 record when the filter ran here, else None."""
     normals = _normals_callable(normals, ply_filename_out, normals_part)
     polish = _polish_callable(polish, ply_filename_out, normals_part)
+    counts = None
     if kept is None and largest_component:
         vd = verts_d if isinstance(verts_d, torch.Tensor) else torch.as_tensor(np.asarray(verts_d))
         fd = faces_d if isinstance(faces_d, torch.Tensor) else torch.as_tensor(np.asarray(faces_d))
@@ -228,6 +231,8 @@ def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename
             kept = moved, kept[1]
         else:
             verts_d = moved
+    if kept_out is not None and kept is not None:
+        kept_out["kept"] = (kept[0], kept[1], counts)
     verts, faces, out_v = place_vertices(verts_d, faces_d, voxel_grid_origin, voxel_size, offset, scale)
     out_f = faces
     if kept is not None:
@@ -258,13 +263,13 @@ def export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename
 
 def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_size, ply_filename_out, offset=None,
                                scale=None, eval_mode=False, task="obman", largest_component=True, data_root="data",
-                               allow_missing_gt=False, normals=False, normals_part=None, polish=False):
+                               allow_missing_gt=False, normals=False, normals_part=None, polish=False, kept_out=None):
     """Iso-surface of one SDF volume -> .ply (utils/mesh.py:331-399).  Returns (verts, faces, trans, scale) with
     verts / faces the raw marching-cubes output like the reference.  MC failures are logged and skipped exactly
     like the reference (utils/mesh.py:353-358).  The written file holds the largest watertight component when the
     surface splits into several (utils/mesh.py:371-381, K8 / alignsdf_amd.mesh_post); in eval mode it is first aligned to
     the ground-truth mesh by the translate+scale ICP (utils/mesh.py:385-395, alignsdf_amd.icp) and `trans`, `scale`
-    are the ICP's; otherwise they are zeros / one.  `normals`, `normals_part`, `polish`: see export_surface."""
+    are the ICP's; otherwise they are zeros / one.  `normals`, `normals_part`, `polish`, `kept_out`: see export_surface."""
     vol = pytorch_3d_sdf_tensor if isinstance(pytorch_3d_sdf_tensor, torch.Tensor) else torch.as_tensor(np.asarray(pytorch_3d_sdf_tensor))
     if not vol.is_cuda:
         vol = vol.cuda()
@@ -276,7 +281,7 @@ def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_s
         return None, None, np.array([0, 0, 0]), np.array([1])
     return export_surface(verts_d, faces_d, voxel_grid_origin, voxel_size, ply_filename_out, offset, scale, eval_mode, task,
                           largest_component, data_root, allow_missing_gt=allow_missing_gt, normals=normals, normals_part=normals_part,
-                          polish=polish)
+                          polish=polish, **({} if kept_out is None else {"kept_out": kept_out}))
 
 
 # colour per part label of the `--viz` output (the table of utils/mesh.py:305-310)
@@ -359,20 +364,23 @@ def decode_two_pass(hand_branch, obj_branch, decoder, latent_vec, mano_results, 
 
 
 def write_hand_and_object(r, filename, hand_branch, obj_branch, offset=None, scale=None, eval_mode=False, task="obman", after_hand=None,
-                          normals=None, polish=None):
+                          normals=None, polish=None, kept_out=None):
     """<filename>_hand.ply, then <filename>_obj.ply, from the volumes of decode_two_pass.  As in the reference, the object mesh is
     written with the hand mesh's ICP translation / scale as its offset / scale (utils/mesh.py:123-133,186-195); the caller's
     `offset` / `scale` reach it only when the hand branch is off.  `after_hand(verts, faces, offset, scale, stats)` runs between the
     two files when the hand has a surface.  `normals`: the evaluator, still bound to this sample - the files then carry vertex normals
     and the stats their `normals_degenerate_<part>` counts.  `polish`: the same evaluator - the written vertices are moved onto the
-    zero level of their own head first (export_surface) and the stats carry `polish_<part>` (project.count_record).  Returns the
-    per-surface (V, F) counts."""
+    zero level of their own head first (export_surface) and the stats carry `polish_<part>` (project.count_record).  `kept_out` (a
+    dict, optional) receives per surface that was written ("hand" / "obj") what its file holds, on the device: export_surface's
+    (verts, faces, counts).  Returns the per-surface (V, F) counts."""
     stats = {}
+    out = {part: {} for part in ("hand", "obj")}
+    keep = lambda part: {} if kept_out is None else {"kept_out": out[part]}
     pol = {part: _polish_callable(polish, "", part) or False for part in ("hand", "obj")}
     fn = {part: VertexNormals(normals, part) if normals is not None else False for part in ("hand", "obj")}
     if hand_branch:
         v, f, offset, scale = convert_sdf_samples_to_ply(r["vol_hand"], r["origin"], r["voxel_size"], filename + "_hand.ply", None,
-                                                         None, eval_mode, task, normals=fn["hand"], polish=pol["hand"])
+                                                         None, eval_mode, task, normals=fn["hand"], polish=pol["hand"], **keep("hand"))
         stats["hand"] = (0, 0) if v is None else (len(v), len(f))
         if polish is not None and v is not None:
             stats["polish_hand"] = pol["hand"].counts
@@ -382,19 +390,21 @@ def write_hand_and_object(r, filename, hand_branch, obj_branch, offset=None, sca
             after_hand(v, f, offset, scale, stats)
     if obj_branch:
         v, f, _, _ = convert_sdf_samples_to_ply(r["vol_obj"], r["origin"], r["voxel_size"], filename + "_obj.ply", offset, scale,
-                                                False, normals=fn["obj"], polish=pol["obj"])
+                                                False, normals=fn["obj"], polish=pol["obj"], **keep("obj"))
         stats["obj"] = (0, 0) if v is None else (len(v), len(f))
         if polish is not None and v is not None:
             stats["polish_obj"] = pol["obj"].counts
         if normals is not None and v is not None:
             stats["normals_degenerate_obj"] = fn["obj"].degenerate
+    if kept_out is not None:
+        kept_out.update({part: o["kept"] for part, o in out.items() if "kept" in o})
     return stats
 
 
 def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, latent_vec, mano_results, obj_results, cam_intr,
                                  specs, filename, N=256, max_batch=32 ** 3, offset=None, scale=None, device="cpu",
                                  label_out=False, viz=False, eval_mode=False, task="obman", grid_mode="reference", return_stats=False,
-                                 normals=False, polish=False):
+                                 normals=False, polish=False, interaction=None):
     """Hand + object meshes of one sample (utils/mesh.py:17-195): writes <filename>_hand.ply / _obj.ply.
     `max_batch` and `device` are accepted for signature compatibility; chunking is internal to the kernel and
     the decoder's device is used.  `grid_mode="reference"` reproduces the true-division lattice of
@@ -410,10 +420,18 @@ def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, l
     not cover raises NotImplementedError before anything is swept.
     `polish=True`: the written vertices of both files are moved onto the zero level of their surface's own head (Newton projection,
     at most one fine voxel per axis: project.polish_vertices) - same faces and vertex count, normals taken at the polished positions,
-    `polish_hand` / `polish_obj` in the stats; an evaluator that cannot project raises NotImplementedError before anything is swept."""
+    `polish_hand` / `polish_obj` in the stats; an evaluator that cannot project raises NotImplementedError before anything is swept.
+    `interaction={"contact_m": 0.005}`: the stats carry `interaction` - penetration depth, intersection volume and contact of the two
+    surfaces from the decoder's own SDFs (interaction.measure_surfaces, the dict of interaction.interaction_record), measured on the
+    very vertices the files hold (write_hand_and_object hands them over on the device), in the decoder's frame (before the eval-mode ICP); ValueError before anything is swept when a branch is
+    off.  The files themselves are the ones written without it."""
     decoder.eval() if hasattr(decoder, "eval") else None
     evaluator = None
-    if normals or polish:
+    contact_m = None
+    if interaction is not None and interaction is not False:
+        from ..interaction import check_option
+        contact_m = check_option(interaction, dict(specs, HandBranch=hand_branch, ObjectBranch=obj_branch))
+    if normals or polish or contact_m is not None:
         evaluator = decoder_for(decoder, specs, mano_results)
     if normals:
         require_normals(evaluator)
@@ -433,6 +451,12 @@ def create_mesh_combined_decoder(hand_branch, obj_branch, cls_branch, decoder, l
         write_label_outputs(vertices, f, labels, filename + "_hand", offset, scale, viz)
         stats["labels"] = labels
 
+    kept = {}          # with the interaction option: part -> what its file holds, on the device
     stats = write_hand_and_object(r, filename, hand_branch, obj_branch, offset, scale, eval_mode, task, label_pass if label_out else None,
-                                  normals=evaluator if normals else None, polish=evaluator if polish else None)
+                                  normals=evaluator if normals else None, polish=evaluator if polish else None,
+                                  **({} if contact_m is None else {"kept_out": kept}))
+    if contact_m is not None:
+        from ..interaction import measure_surfaces
+        bind_sample(evaluator, specs, latent_vec, mano_results, obj_results, cam_intr)      # (whatever ran in between)
+        stats["interaction"] = measure_surfaces(evaluator, r, kept, specs, contact_m)
     return stats if return_stats else None

@@ -506,6 +506,44 @@ int asdf_sample_surface(const float* verts_dev, const int32_t* faces_dev, int32_
 int asdf_icp_normalise(const double* src_dev, int32_t ns, const double* tgt_dev, int32_t nt, double* src_out_dev, double* stats_mapped,
                        void* stream);
 
+/* ---- Hand-object interaction from two signed distance fields (csrc/interaction.hip).  No counterpart at inference time in the
+ * reference: it trains on penetration and contact of the two predicted fields (train.py:563-577) and reports neither.  With two SDFs no
+ * mesh-mesh test is needed - the fields answer.  Neither call needs a decoder, neither synchronises with the host, and both initialise
+ * their record in `stream` order before they accumulate into it (two and three launches).
+ *
+ * OVERLAP RECORD, int32[ASDF_OVERLAP_WORDS], of asdf_interaction_lattice: one streaming pass over two [n0][n1][n2] fp32 device volumes
+ * on the same lattice.  Only SIGNS are read, so the record also holds for the volumes of one-plane sweeps (exact next to the level,
+ * sign-correct elsewhere).  "Negative" is `value < 0` as in asdf_neg_bbox: -0.0 and NaN are not negative.
+ * Both pointers need 4-byte alignment only: the body that is 16-byte aligned in the hand volume is read with 16-byte loads (the object
+ * volume too where it sits alike), the up to three floats before and after it one by one.
+ * ASDF_EINVAL: a NULL or misaligned pointer, a dimension < 1, more than 2^30 voxels (1024^3: every word fits int32). */
+#define ASDF_OVERLAP_HAND 0   /* voxels negative in the hand volume */
+#define ASDF_OVERLAP_OBJ 1    /* voxels negative in the object volume */
+#define ASDF_OVERLAP_BOTH 2   /* voxels negative in both: the intersection */
+#define ASDF_OVERLAP_NAN 3    /* voxels where either value is NaN */
+#define ASDF_OVERLAP_MIN 4    /* [4..6] smallest index per axis of the both-negative voxels (INT_MAX when there is none) */
+#define ASDF_OVERLAP_MAX 7    /* [7..9] largest index per axis (-1 when there is none) */
+#define ASDF_OVERLAP_WORDS 16 /* [10..15] zero */
+int asdf_interaction_lattice(const float* vol_hand_dev, const float* vol_obj_dev, int32_t n0, int32_t n1, int32_t n2, int32_t* rec_dev,
+                             void* stream);
+
+/* CONTACT RECORD, int32[ASDF_CONTACT_WORDS] (8-byte aligned), of asdf_interaction_points: a reduction over the first
+ * n = min(max(*count_dev, 0), cap) of the fp32 values sdf_dev [cap] - one surface's vertices evaluated in the OTHER surface's field.
+ * count_dev is a device word read when the kernel runs (NULL: n = cap), like num_faces_dev of asdf_sample_surface: the kept count
+ * of K8 never crosses to the host for this.  tau >= 0 is the contact distance in the units of the values.
+ * The minimum is taken on mc33.hip's order-preserving key packed with the index into one 64-bit atomic minimum: deterministic, ties
+ * to the lowest index, and the key's order puts -0.0 below +0.0.  NaNs are counted and otherwise skipped.
+ * cap == 0 is ASDF_OK (the record of nothing).  ASDF_EINVAL: cap < 0, NULL sdf_dev with cap > 0, NULL or misaligned rec_dev, tau NaN
+ * or < 0. */
+#define ASDF_CONTACT_COUNT 0     /* values considered (n) */
+#define ASDF_CONTACT_INSIDE 1    /* f < 0 */
+#define ASDF_CONTACT_NEAR 2      /* f <= tau: inside, or within the contact distance outside */
+#define ASDF_CONTACT_NAN 3       /* NaN values */
+#define ASDF_CONTACT_MIN_BITS 4  /* raw fp32 bits of the smallest value (+inf when no value was taken) */
+#define ASDF_CONTACT_ARGMIN 5    /* lowest index that attains it (-1 when none) */
+#define ASDF_CONTACT_WORDS 8     /* [6..7] zero */
+int asdf_interaction_points(const float* sdf_dev, int32_t cap, const int32_t* count_dev, float tau, int32_t* rec_dev, void* stream);
+
 /* ---- Translate + scale ICP of the reference's eval mode: ICP_T_S.run_icp_f (deep_sdf/metrics/icp_trans_scale.py:33-113),
  * called from utils/mesh.py:385-395.  src_dev [ns][3] are the ALREADY NORMALISED source samples (sample_mesh :25-31),
  * tgt_dev [nt][3] the target samples, both fp64 on the device.  Runs until the reference's stopping rules fire
