@@ -36,6 +36,9 @@ EXPORTS = (
     "asdf_decoder_set_sample_host", "asdf_decoder_set_cluster_timeout", "asdf_set_mfma_shape", "asdf_get_mfma_shape",
     "asdf_debug_pack_host_f16w", "asdf_decoder_set_sample_pixel", "asdf_decode_points_grad", "asdf_trace_rays",
     "asdf_project_points", "asdf_interaction_lattice", "asdf_interaction_points",
+    # (added without a new ABI_VERSION - the number is pinned by the tests of three earlier features: a library from before this
+    # entry point fails at its symbol lookup instead)
+    "asdf_decode_points_vjp",
 )
 MATH_F32, MATH_F16X3 = 0, 1
 MAX_CLASSES = 8
@@ -139,6 +142,7 @@ def lib():
     L.asdf_mc_emit_bounded.argtypes = [vp, i32, i32, i32, ctypes.c_double, vp, ctypes.c_size_t, vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp]
     L.asdf_decode_points.argtypes = [vp, vp, i64, vp, vp, vp]
     L.asdf_decode_points_grad.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
+    L.asdf_decode_points_vjp.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.asdf_trace_rays.argtypes = [vp, vp, i64, vp] + [vp] * 8 + [vp]
     L.asdf_project_points.argtypes = [vp, vp, i64, i32, vp] + [vp] * 6 + [vp]
     L.asdf_decoder_set_classifier.argtypes = [vp, vp, vp, i32]

@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libalignsdf_hip.so")
-SOURCES = ["decoder.hip", "k1_kernels.hip", "k1pa_kernels.hip", "k1g_kernels.hip", "k1t_kernels.hip", "k1p_kernels.hip", "k1_cls_kernels.hip", "k1h_kernels.hip", "k1hw_kernels.hip", "k1h_nerf_kernels.hip", "k1s_kernels.hip", "k1s_nerf_kernels.hip", "mc33.hip", "icp.hip", "mesh_cc.hip", "surface_sample.hip", "interaction.hip"]
+SOURCES = ["decoder.hip", "k1_kernels.hip", "k1pa_kernels.hip", "k1g_kernels.hip", "k1v_kernels.hip", "k1t_kernels.hip", "k1p_kernels.hip", "k1_cls_kernels.hip", "k1h_kernels.hip", "k1hw_kernels.hip", "k1h_nerf_kernels.hip", "k1s_kernels.hip", "k1s_nerf_kernels.hip", "mc33.hip", "icp.hip", "mesh_cc.hip", "surface_sample.hip", "interaction.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"]
 # MFMA accumulators in VGPRs (the compiler's default heuristic puts them in AGPRs at this register pressure and the epilogues then read
@@ -32,6 +32,10 @@ TU_FLAGS = {"k1hw_kernels.hip": UNROLL_ALL, "k1s_kernels.hip": VGPR_FORM, "k1s_n
             "k1t_kernels.hip": VGPR_FORM,
             # (the projection form: the gradient form's tile body inside a loop, built like it)
             "k1p_kernels.hip": VGPR_FORM,
+            # (the reverse-mode form: 256 + 242 registers and no scratch this way.  Its last layer loop is left rolled at the default unroll
+            # threshold (indexed registers, 2.5 KB of scratch); with the SLP vectorizer on, pairs of its reduction's products become
+            # 64-bit register tuples and ~480 values spill)
+            "k1v_kernels.hip": VGPR_FORM + ["-mllvm", "-pragma-unroll-threshold=200000", "-fno-slp-vectorize"],
             "k1_cls_kernels.hip": VGPR_FORM}
 
 

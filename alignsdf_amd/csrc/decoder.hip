@@ -99,7 +99,12 @@ struct asdf_decoder {
   float* pa_ws;           // [num_cus][kPixelWsFloats] workspace of the pixel-aligned kernel
   float* pa_lat;          // [2][kLatent]: the channel mean of F, zeros
   unsigned long long* trace_queue;   // [2] device words: the per-head ray queues of asdf_trace_rays (cleared in stream order per call)
+  // reverse mode (asdf_decode_points_vjp): the transposed weight image (null for decoders the form does not cover) and, allocated on
+  // first use, the workgroups' partial sums [num_cus][kVjpFoldFloats] followed by one d_fold block for callers that pass none
+  float* streamT;
+  float* vjp_partial;
 };
+static constexpr int kVjpFoldFloats = kHeads * 2 * kHidden * 4;      // d_fold: [heads][layer 0 / 2][512][4] (sdf_mlp_vjp_kernel.h)
 static constexpr int kShortClusters = kClusterCap / kWavePts * kHeads;      // 128
 static constexpr int kNearCap = ASDF_NEAR_CAP;      // near-level refinement list of a split-half sweep
 static constexpr int kCandCap = ASDF_CAND_CAP;      // box candidates of asdf_decode_grid_box (a head without a certainly negative voxel - a thin
@@ -547,7 +552,7 @@ void asdf_decoder_destroy(asdf_decoder_t* d) {
   void* bufs[] = {d->stream, d->wlat, d->wpt, d->bias02, d->cst, d->embed, d->cls, d->stream16, d->cst16, d->stream16_hi, d->a16, d->cst16p1,
                   d->pa_proj, d->pa_cstb, d->pa_ws, d->pa_lat, d->shortp.xchg, d->shortp.arrivals, d->band_mark, d->box_aux, d->band_idx,
                   d->band_count, d->status, d->latent_stage, d->near_idx, d->near_count, d->audit_rec, d->audit_idx, d->audit_count,
-                  d->trace_queue};
+                  d->trace_queue, d->streamT, d->vjp_partial};
   for (void* b : bufs) (void)hipFree(b);       // (a null pointer is a no-op)
   std::free(d->cst_host);
   std::free(d->cst16_host);
@@ -592,6 +597,7 @@ int asdf_decoder_create(const asdf_decoder_spec_t* spec, const asdf_head_params_
     if (e == hipSuccess) e = hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice);
   };
   up(&d->stream, stream); up(&d->wlat, wlat); up(&d->wpt, wpt); up(&d->bias02, b02); up(&d->cst, cst); up(&d->embed, emb);
+  if (!hp.streamT.empty() && d->kp == 2) up(&d->streamT, hp.streamT);
   d->math = ASDF_MATH_F32;
   if (e == hipSuccess) {
     if (!pack_decoder_f16(*spec, heads, hp)) { asdf_decoder_destroy(d); return ASDF_ENOMEM; }
@@ -638,6 +644,7 @@ int asdf_decoder_create(const asdf_decoder_spec_t* spec, const asdf_head_params_
   if (e == hipSuccess) e = k1g_prepare();
   if (e == hipSuccess) e = k1t_prepare();
   if (e == hipSuccess) e = k1p_prepare();
+  if (e == hipSuccess) e = k1v_prepare();
   if (e == hipSuccess) e = hipMalloc((void**)&d->trace_queue, 2 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc((void**)&d->latent_stage, kLatent * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&d->status, ASDF_STATUS_WORDS * sizeof(int));
@@ -748,6 +755,12 @@ int asdf_decoder_set_sample_pixel(asdf_decoder_t* d, const float* feat_dev, int3
       d->spec.point_feats[1] != 3)
     return ASDF_EINVAL;
   hipStream_t st = (hipStream_t)stream;
+  if (d->streamT) {
+    // a decoder that binds pixel-aligned samples is one the reverse-mode form never accepts: its transposed weight image (4 MiB) goes
+    ASDF_HIP(hipDeviceSynchronize());
+    ASDF_HIP(hipFree(d->streamT));
+    d->streamT = nullptr;
+  }
   const CstOffsets co = cst_offsets(2);
   const size_t hw = (size_t)H * W, need = (size_t)kHeads * 2 * hw * kHidden;
   if (need > d->pa_proj_floats) {
@@ -971,6 +984,43 @@ int asdf_decode_points_grad(asdf_decoder_t* d, const float* xyz_dev, int64_t M, 
   GradParams g;
   g.grad0 = grad_hand_dev; g.grad1 = grad_obj_dev;
   k1g_launch(p, g, k1g_grid(M, d->num_cus), st);
+  ASDF_HIP(hipGetLastError());
+  return ASDF_OK;
+}
+
+int asdf_decode_points_vjp(asdf_decoder_t* d, const float* xyz_dev, int64_t M, const float* w_hand_dev, const float* w_obj_dev,
+                           float* sdf_hand_dev, float* sdf_obj_dev, float* d_fold_dev, float* d_latent_dev, float* d_embed_dev, void* stream) {
+  if (!d || M < 0 || (M > 0 && !xyz_dev)) return ASDF_EINVAL;
+  if (!d->sample_bound) return ASDF_EINVAL;
+  // SeparateDecoder with affine point features and an ordinary (per-sample constant) latent
+  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound || !d->streamT) return ASDF_ENOGRAD;
+  hipStream_t st = (hipStream_t)stream;
+  const int heads_mask = (w_hand_dev ? 1 : 0) | (w_obj_dev ? 2 : 0);
+  if (M == 0 || !heads_mask) {
+    if (d_fold_dev) ASDF_HIP(hipMemsetAsync(d_fold_dev, 0, kVjpFoldFloats * sizeof(float), st));
+    if (d_latent_dev) ASDF_HIP(hipMemsetAsync(d_latent_dev, 0, kLatent * sizeof(float), st));
+    if (d_embed_dev) ASDF_HIP(hipMemsetAsync(d_embed_dev, 0, (size_t)kHeads * ASDF_MAX_POINT_FEATS * 4 * sizeof(float), st));
+    return ASDF_OK;
+  }
+  if (!d->vjp_partial) {      // (first use; sized for the largest grid, so no call allocates after it)
+    const hipError_t e = hipMalloc((void**)&d->vjp_partial, ((size_t)d->num_cus + 1) * kVjpFoldFloats * sizeof(float));
+    if (e != hipSuccess) { g_last_hip_error = (int)e; d->vjp_partial = nullptr; return e == hipErrorOutOfMemory ? ASDF_ENOMEM : ASDF_EHIP; }
+  }
+  // always the fp32 chain's weights and constants: d->math and the MFMA shape of the split-half sweeps are not looked at
+  DecodeParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.stream = d->stream; p.cst = d->cst;
+  p.sdf0 = w_hand_dev ? sdf_hand_dev : nullptr; p.sdf1 = w_obj_dev ? sdf_obj_dev : nullptr;
+  p.xyz = xyz_dev; p.P = M; p.N = 1; p.mode = kPointList;
+  p.first_mlp = w_hand_dev ? 0 : 1;
+  p.num_mlps = heads_mask == 3 ? 2 : 1;
+  p.pf = d->spec.point_feats[0];
+  VjpParams v;
+  v.streamT = d->streamT; v.w[0] = w_hand_dev; v.w[1] = w_obj_dev; v.partial = d->vjp_partial;
+  const int grid = k1v_grid(M, d->num_cus);
+  k1v_launch(p, v, grid, st);
+  float* fold = d_fold_dev ? d_fold_dev : d->vjp_partial + (size_t)d->num_cus * kVjpFoldFloats;
+  k1v_finish(d->vjp_partial, grid, heads_mask, fold, d->wlat, d->wpt, ASDF_MAX_POINT_FEATS, d_latent_dev, d_embed_dev, st);
   ASDF_HIP(hipGetLastError());
   return ASDF_OK;
 }

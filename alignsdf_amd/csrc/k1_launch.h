@@ -48,6 +48,20 @@ struct GradParams {
 hipError_t k1g_prepare();
 int k1g_grid(long long points, int num_cus);      // workgroups of a launch over `points` points (32 per workgroup tile)
 void k1g_launch(const DecodeParams& p, const GradParams& g, int grid, hipStream_t st);
+// the fp32 chain in reverse mode over a point list (k1v_kernels.hip, sdf_mlp_vjp_kernel.h): sdf and, for weights dL / d sdf, the gradient
+// with respect to the folded per-sample constants, the latent code and the point embedding; SeparateDecoder, affine point features
+struct VjpParams {
+  const float* streamT; // [heads][kStagesHead][kStageFloats]: W3^T, W2a^T, W1^T as stages (pack_decoder)
+  const float* w[2];    // [P] dL / d sdf of the hand / object head; a head is evaluated only when its weights are given
+  float* partial;       // [grid][heads][2 (layer 0, layer 2)][512][4]: one block of sums per workgroup
+};
+hipError_t k1v_prepare();
+int k1v_grid(long long points, int num_cus);      // workgroups of a launch over `points` points (128 per workgroup tile)
+void k1v_launch(const DecodeParams& p, const VjpParams& v, int grid, hipStream_t st);
+// behind it: partial -> d_fold [heads][2][512][4] (heads_mask: bit h = head h was evaluated), then the adjoint of the per-sample fold,
+// d_fold -> d_latent [256] / d_embed [heads][max_pf][4] (each may be null)
+void k1v_finish(const float* partial, int grid, int heads_mask, float* d_fold, const float* wlat, const float* wpt, int max_pf,
+                float* d_latent, float* d_embed, hipStream_t st);
 // sphere tracing on the fp32 chain (k1t_kernels.hip): one ray per MFMA column, free columns refilled from a per-head queue;
 // SeparateDecoder, affine point features.  The rule: sdf_mlp_trace_kernel.h
 struct TraceRule {

@@ -11,6 +11,8 @@ namespace asdf {
 
 struct HostPack {
   std::vector<float> stream;   // [kStagesAll][kStageFloats]
+  std::vector<float> streamT;  // [kStagesAll][kStageFloats]: the transposed image of the reverse-mode kernel (sdf_mlp_vjp_kernel.h), per head
+                               // W3^T (16 tiles x 4 stages), W2a^T (8 x 4), W1^T (16 x 2); SeparateDecoder with affine features, else empty
   std::vector<float> wlat;     // [heads][2][512][256]   latent columns of layers 0 and 2
   std::vector<float> wpt;      // [heads][2][512][ASDF_MAX_POINT_FEATS]  point columns of layers 0 and 2
   std::vector<float> b02;      // [heads][2][512]
@@ -167,6 +169,8 @@ inline bool pack_decoder(const asdf_decoder_spec_t& spec, const asdf_head_params
     hp.b02.assign((size_t)kHeads * 2 * kHidden, 0.f);
     hp.cst.assign((size_t)kHeads * co.floats, 0.f);
     hp.emb.assign((size_t)kHeads * ASDF_MAX_POINT_FEATS * 4, 0.f);
+    hp.streamT.clear();
+    if (spec.num_heads == 2 && spec.feature_mode == ASDF_FEATURES_AFFINE) hp.streamT.assign((size_t)kStagesAll * kStageFloats, 0.f);
   } catch (...) {
     return false;
   }
@@ -206,6 +210,13 @@ inline bool pack_decoder(const asdf_decoder_spec_t& spec, const asdf_head_params
     pack(kTilesL1, 4, [&](int row, int feat) { return row < n1 ? W1[(size_t)row * kHidden + feat] : 0.0f; });
     pack(kTilesHidden, 2, [&](int row, int feat) { return feat < n1 ? W2[(size_t)row * kHidden + feat] : 0.0f; });
     pack(kTilesHidden, 4, [&](int row, int feat) { return W3[(size_t)row * kHidden + feat]; });
+    if (!hp.streamT.empty()) {
+      // the same stages of the transposed matrices (row = the layer's INPUT feature, feat = its output row), in the reverse pass's order
+      sp = &hp.streamT[(size_t)h * kStagesHead * kStageFloats];
+      pack(kTilesHidden, 4, [&](int row, int feat) { return W3[(size_t)feat * kHidden + row]; });
+      pack(kTilesL1, 4, [&](int row, int feat) { return row < n1 ? W2[(size_t)feat * kHidden + row] : 0.0f; });
+      pack(kTilesHidden, 2, [&](int row, int feat) { return feat < n1 ? W1[(size_t)feat * kHidden + row] : 0.0f; });
+    }
     // static constants in D-layout order
     float* c = &hp.cst[(size_t)h * co.floats];
     for (int t = 0; t < kTilesHidden; ++t)

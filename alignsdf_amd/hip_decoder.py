@@ -206,6 +206,23 @@ def grad_refusal(combined, point_feat_size, encode_style, pixel_align):
     return None
 
 
+def vjp_refusal(combined, point_feat_size, encode_style, pixel_align):
+    """Why (a string) the reverse-mode form of the fp32 chain (HipSdfDecoder.decode_points_vjp, csrc/k1v_kernels.hip) does not cover a
+    decoder of this shape, or None.  Its coverage is the gradient kernel's: SeparateDecoder with point features affine in xyz."""
+    if combined:
+        return "CombinedDecoder (the reverse-mode kernel is built for SeparateDecoder)"
+    if pixel_align:
+        return "pixel-aligned latent (the bicubic gather is not differentiated)"
+    if encode_style == "nerf" and int(point_feat_size) > 3:
+        return "NeRF encoding with PointFeatSize %d (only point features affine in xyz are built)" % int(point_feat_size)
+    return None
+
+
+# what decode_points_vjp returns (HipSdfDecoder and TorchModuleDecoder): sdf_* [M] or None, d_latent [L], d_embed = (hand [pf_h, 4],
+# obj [pf_o, 4]) or None, d_fold [2, 2, 512, 4] or None
+SdfVjp = collections.namedtuple("SdfVjp", "sdf_hand sdf_obj d_latent d_embed d_fold")
+
+
 def trace_refusal(combined, point_feat_size, encode_style, pixel_align):
     """Why (a string) the ray-tracing form of the fp32 chain (HipSdfDecoder.trace_rays, csrc/k1t_kernels.hip) does not cover a decoder
     of this shape, or None.  Its coverage is the gradient kernel's: SeparateDecoder with point features affine in xyz."""
@@ -1346,6 +1363,45 @@ class HipSdfDecoder:
             raise NotImplementedError("the gradient kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
         _native.check(code, "asdf_decode_points_grad")
         return sh, gh, so, go
+
+    def vjp_refusal(self):
+        """vjp_refusal() of this decoder: why decode_points_vjp would refuse, or None."""
+        return vjp_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
+
+    def decode_points_vjp(self, xyz, w_hand=None, w_obj=None, want_sdf=True):
+        """Reverse mode over the normalised query points [M,3] in one launch of the fp32 chain (csrc/k1v_kernels.hip; the math mode of
+        the sweeps is neither read nor changed): for w_hand / w_obj [M] = dL / d sdf of a scalar L, the gradient of L with respect to
+        the bound sample.  Returns SdfVjp(sdf_hand [M], sdf_obj [M], d_latent [L], d_embed = (hand [pf_h, 4], obj [pf_o, 4]) in the
+        layout of set_sample's embedding, d_fold [2, 2, 512, 4] = the gradient with respect to the folded constants of layers 0 and 2)
+        - device tensors, nothing waits for the device.  A head whose weights are None is not evaluated: its sdf is None, its d_embed
+        and d_fold block are zero.  The SDF values are decode_points' under set_math("f32"), bit for bit; every sum is taken in a fixed
+        order, so the same call twice gives the same bits.  NotImplementedError(reason) for a decoder vjp_refusal() does not cover."""
+        why = self.vjp_refusal()
+        if why is not None:
+            raise NotImplementedError("the reverse-mode kernel does not cover this decoder: %s" % why)
+        xyz = xyz.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        M = xyz.shape[0]
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError("xyz has shape %s, expected [M, 3]" % (tuple(xyz.shape),))
+        ws = []
+        for name, w in (("w_hand", w_hand), ("w_obj", w_obj)):
+            if w is not None:
+                w = w.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+                if w.numel() != M:
+                    raise ValueError("%s has %d elements, expected %d" % (name, w.numel(), M))
+            ws.append(w)
+        new = lambda on, *shape: torch.empty(shape, dtype=torch.float32, device=self.device) if on else None
+        sh, so = new(want_sdf and ws[0] is not None, M), new(want_sdf and ws[1] is not None, M)
+        d_fold, d_latent = new(True, 2, 2, 512, 4), new(True, self.latent_size)
+        d_embed = new(True, 2, _native.MAX_POINT_FEATS, 4)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            code = self._L.asdf_decode_points_vjp(self._h, xyz.data_ptr(), M, ptr(ws[0]), ptr(ws[1]), ptr(sh), ptr(so), d_fold.data_ptr(),
+                                                  d_latent.data_ptr(), d_embed.data_ptr(), self._stream())
+        if code == _native.ENOGRAD:
+            raise NotImplementedError("the reverse-mode kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
+        _native.check(code, "asdf_decode_points_vjp")
+        return SdfVjp(sh, so, d_latent, (d_embed[0, :self._pf[0]], d_embed[1, :self._pf[1]]), d_fold)
 
     def trace_refusal(self):
         """trace_refusal() of this decoder: why trace_rays would refuse, or None."""

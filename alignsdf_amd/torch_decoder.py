@@ -287,6 +287,115 @@ class TorchModuleDecoder:
             module.train(was_training)
         return tuple(out)
 
+    def _head_columns(self):
+        """The columns of the module's point-feature vector that the hand / object MLP reads (networks/model.py:288-299), or None where
+        the features are not affine in xyz or the module is not a SeparateDecoder with specs."""
+        specs = self.specs
+        if specs is None or specs.get("PixelAlign", False) or not hasattr(self.module, "linh0"):
+            return None
+        pf, style = int(specs["PointFeatSize"]), specs["EncodeStyle"]
+        if style == "nerf" and pf > 3:
+            return None
+        a = torch.arange(pf, device=self.device)
+        return {"nerf": (a, a), "hand": (a, a[:3]), "obj": (a[:3], a), "both": (a[:-3], torch.cat([a[:3], a[-3:]]))}[style]
+
+    def decode_embedded(self, latent, embed, xyz):
+        """(sdf_hand [M], sdf_obj [M]) of the module at xyz [M, 3] for a latent [L] and point embeddings in HipSdfDecoder.set_sample's
+        layout (feat = E[:, :3] x + E[:, 3]) - as a torch graph: differentiable in all three.
+          SeparateDecoder, features affine in xyz: embed = (hand [pf_h, 4], obj [pf_o, 4]); one module call per head (the two
+            embeddings need not agree on the columns the heads share).
+          CombinedDecoder, features affine in xyz: embed = (E [pf, 4],) - or None for plain xyz; one module call.
+          NeRF-encoded features: embed must be None (no affine embedding exists; the encoding is the module path's own).
+        ValueError for a pixel-aligned decoder (its latent is a feature map, not a code) and a module without specs."""
+        specs = self.specs
+        if specs is None or specs.get("PixelAlign", False):
+            raise ValueError("decode_embedded: a decoder with specs and a per-sample latent code only")
+        module = self.module
+        was_training = module.training
+        module.eval()
+        try:
+            xyz = xyz.to(self.device, torch.float32)
+            lat = latent.reshape(1, -1).to(self.device, torch.float32).expand(xyz.shape[0], -1)
+            pf, style = int(specs["PointFeatSize"]), specs["EncodeStyle"]
+            affine = lambda E: xyz @ E[:, :3].t() + E[:, 3]
+            if style == "nerf" and pf > 3:
+                if embed is not None:
+                    raise ValueError("decode_embedded: a NeRF-encoded decoder takes raw xyz; no affine embedding applies")
+                out = module(torch.cat([lat, nerf_embedding(xyz, (pf - 3) // 6)], 1))
+                return out[0].reshape(-1), out[1].reshape(-1)
+            cols = self._head_columns()
+            if cols is None:                    # CombinedDecoder: the one MLP reads the whole feature vector
+                feats = xyz if embed is None else affine(embed[0].to(self.device, torch.float32))
+                if feats.shape[1] != pf:
+                    raise ValueError("decode_embedded: the embedding gives %d point features, the module reads %d" % (feats.shape[1], pf))
+                out = module(torch.cat([lat, feats], 1))
+                return out[0].reshape(-1), out[1].reshape(-1)
+            if embed is None:
+                if pf != 3:
+                    raise ValueError("decode_embedded: this decoder needs a point embedding per head")
+                embed = (torch.eye(3, 4, device=self.device),) * 2
+            out = []
+            for h, (E, c) in enumerate(zip(embed, cols)):
+                q = torch.zeros(xyz.shape[0], pf, dtype=torch.float32, device=self.device).index_copy(1, c, affine(E.to(self.device, torch.float32)))
+                out.append(module(torch.cat([lat, q], 1))[h].reshape(-1))
+        finally:
+            module.train(was_training)
+        return tuple(out)
+
+    def decode_points_vjp(self, xyz, w_hand=None, w_obj=None, want_sdf=True):
+        """The interface of HipSdfDecoder.decode_points_vjp by torch autograd through the module's own forward on the bound sample:
+        SdfVjp(sdf_hand, sdf_obj, d_latent [L], d_embed, d_fold = None).  d_latent comes from a latent that requires grad; d_embed[h] =
+        g_feat^T [xyz, 1] over head h's own feature columns (g_feat = the gradient with respect to the point features), None for NeRF
+        features.  ValueError for a pixel-aligned sample."""
+        from .hip_decoder import SdfVjp
+        if self._sample is None:
+            raise ValueError("no sample bound: call set_sample first")
+        specs = self.specs
+        if specs is not None and specs.get("PixelAlign", False):
+            raise ValueError("decode_points_vjp: a pixel-aligned sample has no per-sample latent code to differentiate")
+        xyz = xyz.detach().to(self.device, torch.float32).contiguous()
+        M = xyz.shape[0]
+        ws = [None if w is None else w.detach().to(self.device, torch.float32).reshape(-1) for w in (w_hand, w_obj)]
+        for w in ws:
+            if w is not None and w.numel() != M:
+                raise ValueError("weights have %d elements, expected %d" % (w.numel(), M))
+        latent, mano, obj, _ = self._sample
+        cols = self._head_columns()
+        module = self.module
+        was_training = module.training
+        module.eval()
+        sdf = [None, None]
+        d_latent = torch.zeros(latent.numel(), dtype=torch.float32, device=self.device)
+        d_embed = None if cols is None else [torch.zeros(len(c), 4, dtype=torch.float32, device=self.device) for c in cols]
+        try:
+            with torch.enable_grad():
+                for head in range(0, M, CHUNK):
+                    x = xyz[head:head + CHUNK]
+                    lat = latent.detach().reshape(1, -1).clone().requires_grad_()
+                    q = x
+                    if specs is not None and specs["PointFeatSize"] > 3:
+                        if mano is not None and specs["EncodeStyle"] != "nerf":
+                            q = kinematic_embedding(x, mano, specs["PointFeatSize"], specs["SdfScaleFactor"], obj, specs["EncodeStyle"])
+                        else:
+                            q = nerf_embedding(x, (specs["PointFeatSize"] - 3) // 6)
+                    q = q.detach().requires_grad_()
+                    values = module(torch.cat([lat.expand(x.shape[0], -1), q], 1))[:2]
+                    x1 = torch.cat([x, torch.ones(x.shape[0], 1, dtype=torch.float32, device=self.device)], 1)
+                    for k, (w, v) in enumerate(zip(ws, values)):
+                        if w is None or v is None:
+                            continue
+                        if want_sdf:
+                            if sdf[k] is None:
+                                sdf[k] = torch.empty(M, dtype=torch.float32, device=self.device)
+                            sdf[k][head:head + CHUNK] = v.detach().reshape(-1)
+                        g_lat, g_q = torch.autograd.grad((v.reshape(-1) * w[head:head + CHUNK]).sum(), (lat, q), retain_graph=True)
+                        d_latent += g_lat.reshape(-1)
+                        if d_embed is not None:
+                            d_embed[k] += g_q[:, cols[k]].t() @ x1
+        finally:
+            module.train(was_training)
+        return SdfVjp(sdf[0], sdf[1], d_latent, None if d_embed is None else tuple(d_embed), None)
+
     def trace_rays(self, origins, dirs, t0, t1, hand=True, obj=True, max_steps=64, refine_steps=6, step_scale=1.0, min_step=1e-3,
                    max_step=0.05, want_bracket=False, want_evals=False):
         """The interface and the rule of HipSdfDecoder.trace_rays on the module (render.trace_lockstep): per head, all rays in lockstep

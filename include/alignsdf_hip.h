@@ -279,6 +279,31 @@ int asdf_decode_points(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, flo
 int asdf_decode_points_grad(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, float* sdf_hand_dev, float* grad_hand_dev,
                             float* sdf_obj_dev, float* grad_obj_dev, void* stream);
 
+/* Reverse mode of asdf_decode_points: for weights w_*_dev [M] = dL / d sdf of a scalar L, the gradient of L with respect to everything
+ * asdf_decoder_set_sample binds, in one pass of the fp32 MFMA chain forwards and one backwards over the transposed weights under the
+ * forward pass's ReLU masks (csrc/k1v_kernels.hip, csrc/sdf_mlp_vjp_kernel.h; 32 points per wave, 128 per workgroup).  No counterpart in
+ * the reference (it differentiates by torch autograd).  A head whose weights are NULL is not evaluated at all: its sdf output is not
+ * written, its d_fold block and d_embed rows are zero and it adds nothing to d_latent.  Outputs, each may be NULL:
+ *   sdf_*_dev [M]       asdf_decode_points' values under ASDF_MATH_F32, bit for bit;
+ *   d_fold_dev          [2 heads][2 (layer 0, layer 2)][512][4] = (dA[:, 0..2], dc): the gradient with respect to the folded per-sample
+ *                       constants of csrc/sdf_layout.h (h0 = relu(A0 x + c0), h2 = relu(W2a h1 + A2 x + c2)), rows in natural order;
+ *   d_latent_dev [256]  summed over the evaluated heads;
+ *   d_embed_dev         [2][ASDF_MAX_POINT_FEATS][4], the layout of asdf_decoder_set_sample's embedding (feat = E[:, :3] x + E[:, 3]).
+ * The sums over the points are taken in a fixed order without atomics (per wave, per workgroup, then over the workgroups in fp64): two
+ * calls on the same device and list agree in every bit, and a point with w = 0 contributes exactly zero.  The derivative of ReLU at 0
+ * is 0, as in torch.  With M == 0, or both weights NULL, every non-NULL d_* output is written with zeros and nothing else is launched.
+ * The call always runs on the fp32 chain and neither reads nor changes the decoder's math mode or MFMA shape.  Not re-entrant per
+ * decoder: the partial sums live in decoder-owned scratch (allocated by the first call, freed by asdf_decoder_destroy).
+ * ASDF_EINVAL: NULL decoder, no sample bound, M < 0, NULL xyz with M > 0 (nothing is written).  ASDF_ENOGRAD: CombinedDecoder,
+ * NeRF-encoded point features, a pixel-aligned sample - exactly where asdf_decode_points_grad answers so - and every later call on a
+ * decoder that has once bound a pixel-aligned sample (asdf_decoder_set_sample_pixel frees the transposed weight image: only decoders
+ * this form accepts keep one).
+ * (Added without a new ABI version: asdf_version() stays 132, and a loader that wants this entry point looks the symbol up - a library
+ * from before it fails there, not at a version check.) */
+int asdf_decode_points_vjp(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, const float* w_hand_dev, const float* w_obj_dev,
+                           float* sdf_hand_dev, float* sdf_obj_dev, float* d_fold_dev, float* d_latent_dev, float* d_embed_dev,
+                           void* stream);
+
 /* Sphere tracing: the first surface of each head along M ray segments, marched and refined inside one kernel (csrc/k1t_kernels.hip -
  * a ray per column of the fp32 MFMA chain; a column whose ray is done takes the next ray of a device queue).  No counterpart in the
  * reference (it only ever meshes).  rays_dev [M][8] fp32, 16-byte aligned: origin (3), direction (3, need not be a unit vector), t0, t1 -
