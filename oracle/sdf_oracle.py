@@ -9,7 +9,8 @@ Pinning: tests/golden/ref_*.npz hold outputs of the reference itself (imported i
 container by tests/golden/make_ref_goldens.py); tests/test_oracle_decoder.py checks this module
 against them bit for bit (grid, zoom cube) or to 1e-6 (decoder outputs).  decode_points(..., dtype=torch.float64) runs the
 same chain in fp64: the truth the fp32-class GPU kernels are held to (tests/test_oracle_fp64.py, tests/test_gpu_split_half_fp64.py);
-decode_points_pixel is the same for a PixelAlign sample (tests/test_oracle_pixel_align.py, tests/test_gpu_pixel_align_fp64.py).
+decode_points_pixel is the same for a PixelAlign sample (tests/test_oracle_pixel_align.py, tests/test_gpu_pixel_align_fp64.py),
+classify_points(..., dtype=torch.float64) for the label pass (tests/test_cls_truth.py, tests/test_gpu_cls_fp64.py).
 """
 import numpy as np
 import torch
@@ -266,16 +267,23 @@ def decode_points_pixel(state_dict, feat, xyz, specs, mano_results, cam_intr, dt
     return hand, obj
 
 
-def classify_points(state_dict, latent, xyz, specs, mano_results=None, obj_results=None, max_batch=2 ** 18):
+def classify_points(state_dict, latent, xyz, specs, mano_results=None, obj_results=None, max_batch=2 ** 18, dtype=torch.float32):
     """The label pass over explicit points (utils/mesh.py:146-157): `predicted_class` = classifier_head applied to the
     input of the last layer of the hand MLP (SeparateDecoder, networks/model.py:306-307) or of the single MLP
-    (CombinedDecoder, networks/model.py:161-162).  Returns (scores [M, num_class] fp32, labels [M] int64 = argmax)."""
-    params = combined_params(state_dict) if "lin0.bias" in state_dict else effective_head_params(state_dict, "h")
-    wc = torch.as_tensor(state_dict["classifier_head.weight"]).float()
-    bc = torch.as_tensor(state_dict["classifier_head.bias"]).float()
-    latent = torch.as_tensor(latent).float().reshape(1, -1)
-    xyz = torch.as_tensor(xyz).float()
-    scores = torch.zeros(xyz.shape[0], wc.shape[0])
+    (CombinedDecoder, networks/model.py:161-162).  Returns (scores [M, num_class] of `dtype`, labels [M] int64 = argmax).
+
+    dtype=torch.float32 (the default) is the reference's arithmetic.  dtype=torch.float64 runs the weight-norm fold, the pose inputs,
+    the point embedding, the hand (or single) MLP and the classifier head in fp64 on the stored values, as decode_points does: the
+    truth the label-pass kernels are measured against (tests/test_cls_truth.py, tests/test_gpu_cls_fp64.py)."""
+    params = combined_params(state_dict, dtype) if "lin0.bias" in state_dict else effective_head_params(state_dict, "h", dtype)
+    wc = torch.as_tensor(state_dict["classifier_head.weight"]).to(dtype)
+    bc = torch.as_tensor(state_dict["classifier_head.bias"]).to(dtype)
+    if dtype != torch.float32:
+        cast = lambda d: None if d is None else {k: torch.as_tensor(v).to(dtype) for k, v in d.items()}
+        mano_results, obj_results = cast(mano_results), cast(obj_results)
+    latent = torch.as_tensor(latent).to(dtype).reshape(1, -1)
+    xyz = torch.as_tensor(xyz).to(dtype)
+    scores = torch.zeros(xyz.shape[0], wc.shape[0], dtype=dtype)
     with torch.no_grad():
         for head in range(0, xyz.shape[0], max_batch):
             sub = xyz[head:head + max_batch]
