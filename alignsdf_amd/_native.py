@@ -39,6 +39,8 @@ EXPORTS = (
     # (added without a new ABI_VERSION - the number is pinned by the tests of three earlier features: a library from before this
     # entry point fails at its symbol lookup instead)
     "asdf_decode_points_vjp",
+    # (the mesh signed distance unit, csrc/mesh_sdf.hip: looked up by name in the same way)
+    "asdf_mesh_sdf_workspace_bytes", "asdf_mesh_sdf_prepare", "asdf_mesh_sdf_points",
 )
 MATH_F32, MATH_F16X3 = 0, 1
 MAX_CLASSES = 8
@@ -57,6 +59,10 @@ BOX_RANGE_WORDS = (BOX_RANGE, BOX_STRIDE + BOX_RANGE)      # the range words of 
 # The records of csrc/interaction.hip: ASDF_OVERLAP_* / ASDF_CONTACT_* under the same names without the prefix
 OVERLAP_HAND, OVERLAP_OBJ, OVERLAP_BOTH, OVERLAP_NAN, OVERLAP_MIN, OVERLAP_MAX, OVERLAP_WORDS = 0, 1, 2, 3, 4, 7, 16
 CONTACT_COUNT, CONTACT_INSIDE, CONTACT_NEAR, CONTACT_NAN, CONTACT_MIN_BITS, CONTACT_ARGMIN, CONTACT_WORDS = 0, 1, 2, 3, 4, 5, 8
+# csrc/mesh_sdf.hip: ASDF_MESH_SDF_* under the same names without the ASDF_ prefix
+MESH_SDF_BLOCK_FACES, MESH_SDF_CHUNK_FACES, MESH_SDF_RECORD_BYTES, MESH_SDF_SPLIT_MAX_QUERIES = 64, 128, 48, 131072
+MESH_SDF_INFO_SKIPPED, MESH_SDF_INFO_ZERO_AREA, MESH_SDF_INFO_WORDS = 0, 1, 4
+MESH_SDF_SHAPE_AUTO, MESH_SDF_SHAPE_WHOLE, MESH_SDF_SHAPE_SPLIT = 0, 1, 2
 
 
 def box_of(rec, head):
@@ -150,6 +156,9 @@ def lib():
     L.asdf_neg_bbox.argtypes = [vp, i32, i32, i32, vp, vp]
     L.asdf_interaction_lattice.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.asdf_interaction_points.argtypes = [vp, i32, vp, f32, vp, vp]
+    L.asdf_mesh_sdf_workspace_bytes.argtypes = [i32, i64, ctypes.POINTER(ctypes.c_size_t)]
+    L.asdf_mesh_sdf_prepare.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    L.asdf_mesh_sdf_points.argtypes = [vp, i32, vp, i64] + [vp] * 4 + [vp, vp]
     L.asdf_mc_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.asdf_mc_count.argtypes = [vp, i32, i32, i32, ctypes.c_double, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
                                 ctypes.POINTER(ctypes.c_uint32), vp]

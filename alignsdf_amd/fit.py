@@ -119,22 +119,31 @@ def sdf_at_points(decoder, latent, embed, xyz):
     return _NativeSdf.apply(decoder, latent, embed[0], embed[1], xyz)
 
 
-def fit_sample(decoder, latent, embed, surface_hand=None, surface_obj=None, steps=40, lr=2e-3, prior=1e-3, penetration=0.0):
+def fit_sample(decoder, latent, embed, surface_hand=None, surface_obj=None, steps=40, lr=2e-3, prior=1e-3, penetration=0.0,
+               sdf_hand=None, sdf_obj=None, clamp=0.05):
     """Refine a sample against observed surface points: Adam over the latent code z and one rigid shift per head (shift_embed) on
         mean |f_hand(surface_hand)| + mean |f_obj(surface_obj)| + prior mean((z - z0)^2) + penetration mean(relu(-f_obj(surface_hand)))
-    with z0 the code it starts from.  surface_* [n, 3] in the decoder's normalised space (None: that term is absent).  Returns
-    (latent, embed, shifts, history): the fitted code [L] and embeddings, the two shifts [2, 3] and, per step, the first two terms of
-    the loss taken before that step."""
+    with z0 the code it starts from.  surface_* [n, 3] in the decoder's normalised space (None: that term is absent).
+    sdf_hand / sdf_obj: an (xyz [m, 3], sdf [m]) pair each, in the same space (mesh_sdf.sdf_samples makes them): that head gains the
+    auto-decoder's own term mean |clip(f, -clamp, clamp) - clip(s, -clamp, clamp)|, which - unlike |f| on the surface - says which
+    side is inside.  Returns (latent, embed, shifts, history): the fitted code [L] and embeddings, the two shifts [2, 3] and, per
+    step, the data terms of the loss (all but prior and penetration) taken before that step."""
     dev = decoder.device
     z0 = latent.detach().reshape(-1).to(dev, torch.float32)
     z = z0.clone().requires_grad_()
     E0 = [torch.as_tensor(np.asarray(e, np.float64) if not torch.is_tensor(e) else e.detach()).to(dev, torch.float32) for e in embed]
     shifts = torch.zeros(2, 3, dtype=torch.float32, device=dev, requires_grad=True)
     sets = [None if s is None else torch.as_tensor(s).detach().to(dev, torch.float32).reshape(-1, 3) for s in (surface_hand, surface_obj)]
-    if sets[0] is None and sets[1] is None:
+    valued = [None if s is None else (torch.as_tensor(s[0]).detach().to(dev, torch.float32).reshape(-1, 3),
+                                      torch.as_tensor(s[1]).detach().to(dev, torch.float32).reshape(-1).clamp(-clamp, clamp))
+              for s in (sdf_hand, sdf_obj)]
+    if all(s is None for s in sets + valued):
         raise ValueError("fit_sample: no surface points")
-    pts = torch.cat([s for s in sets if s is not None], 0)
+    pts = torch.cat([s for s in sets if s is not None] + [s[0] for s in valued if s is not None], 0)
     n_hand = 0 if sets[0] is None else sets[0].shape[0]
+    first = [0, 0]                                     # where each head's valued points begin in pts
+    first[0] = n_hand + (0 if sets[1] is None else sets[1].shape[0])
+    first[1] = first[0] + (0 if valued[0] is None else valued[0][0].shape[0])
     opt = torch.optim.Adam([z, shifts], lr=lr)
     history = []
     for _ in range(steps):
@@ -145,7 +154,10 @@ def fit_sample(decoder, latent, embed, surface_hand=None, surface_obj=None, step
         if sets[0] is not None:
             data = data + f_hand[:n_hand].abs().mean()
         if sets[1] is not None:
-            data = data + f_obj[n_hand:].abs().mean()
+            data = data + f_obj[n_hand:n_hand + sets[1].shape[0]].abs().mean()
+        for f, v, at in ((f_hand, valued[0], first[0]), (f_obj, valued[1], first[1])):
+            if v is not None:
+                data = data + (f[at:at + v[0].shape[0]].clamp(-clamp, clamp) - v[1]).abs().mean()
         loss = data + prior * ((z - z0) ** 2).mean()
         if penetration and sets[0] is not None:
             loss = loss + penetration * torch.relu(-f_obj[:n_hand]).mean()

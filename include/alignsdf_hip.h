@@ -569,6 +569,68 @@ int asdf_interaction_lattice(const float* vol_hand_dev, const float* vol_obj_dev
 #define ASDF_CONTACT_WORDS 8     /* [6..7] zero */
 int asdf_interaction_points(const float* sdf_dev, int32_t cap, const int32_t* count_dev, float tau, int32_t* rec_dev, void* stream);
 
+/* ---- Signed distance field of a triangle mesh (csrc/mesh_sdf.hip).  No counterpart in the reference tree: its (xyz, sdf) samples come
+ * from an external tool.  Plain device arrays in and out, no decoder, nothing waits for the stream.
+ *
+ * THE RULE, for a mesh (verts fp32 [V][3], faces int32 [T][3]) and a query p, all arithmetic in fp32 without contraction,
+ * u.v = (u.x v.x + u.y v.y) + u.z v.z:
+ * A face's corners (a, b, c) are taken in the order of their VERTEX INDICES, lowest first, and sigma = +1 when that order is an even
+ * permutation of the face's own, -1 when it is odd: the distance half never sees the orientation, the winding half sees it as a sign.
+ *   d(p)       the minimum over the faces of the Euclidean distance from p to the CLOSED triangle (a, b, c) - no infinite planes.  With
+ *              ab = b - a, ac = c - a, bc = c - b, ap = p - a, bp = p - b, cp = p - c, d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp,
+ *              d5 = ab.cp, d6 = ac.cp, vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4 the closest point q is, first match:
+ *                d1 <= 0 and d2 <= 0: a;   d3 >= 0 and d4 <= d3: b;   vc <= 0, d1 >= 0, d3 <= 0: a + (d1 / (d1 - d3)) ab;
+ *                d6 >= 0 and d5 <= d6: c;  vb <= 0, d2 >= 0, d6 <= 0: a + (d2 / (d2 - d6)) ac;
+ *                va <= 0, d4 - d3 >= 0, d5 - d6 >= 0: b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) bc;
+ *                else the interior: (a + (vb / s) ab) + (vc / s) ac with s = (va + vb) + vc
+ *              and the squared distance (p - q).(p - q).  A ZERO-AREA face - one whose cross product ab x ac, as computed, is exactly
+ *              the zero vector - is the segment or point it actually is: the nearest of the closest points on its three edges ab, bc
+ *              and ca (in this order, strict <), each base + clamp(((p - base).e) / (e.e), 0, 1) e, or base when e.e == 0.
+ *   face(p)    the lowest face index that attains the minimum of the squared distances AS COMPUTED (faces in index order, strict <);
+ *   closest(p) q of that face; d = sqrt of its squared distance;
+ *   w(p)       the generalised winding number S / fp32(2 pi), S the sum over the faces of sigma atan2(det, den) in the van Oosterom-Strackee
+ *              form (the solid angle is twice that): A = a - p, B = b - p, C = c - p, det = A.(B x C),
+ *              den = (((|A| |B|) |C| + (A.B) |C|) + (B.C) |A|) + (C.A) |B|.  A zero-area face contributes exactly nothing.
+ *              S is DEFINED as the fp32 sum, in chunk order and starting from +0, of per-chunk fp32 sums taken in face order from +0;
+ *              a chunk is ASDF_MESH_SDF_CHUNK_FACES consecutive face indices.  That makes w - like everything else here - a function
+ *              of the query and the mesh alone: not of M, of the query's place in the list or of how the launch was shaped (there are
+ *              no atomics on any result).
+ *   sdf(p)     -d if |w| >= 0.5, else +d: a consistently inward-oriented mesh behaves like an outward one (the same sdf bits, -w).  Open or self-intersecting
+ *              meshes get what this rule says; nothing is repaired.
+ * A face with an index outside [0, V) or a non-finite corner is ABSENT: it contributes nothing to d and w (it keeps its index), is
+ * counted in info_dev, and no index, however bad, is used for a read.  A mesh with no face left: sdf = +inf, w = 0, face = -1,
+ * closest = NaN.  A query with a non-finite coordinate: sdf = NaN, w = NaN, face = -1, closest = NaN.
+ *
+ * asdf_mesh_sdf_workspace_bytes: M == 0 -> the bytes of the workspace asdf_mesh_sdf_prepare fills for num_faces faces; M > 0 -> the
+ *   bytes of scratch_dev for a call of asdf_mesh_sdf_points with M queries against that mesh (at least 16).
+ * asdf_mesh_sdf_prepare, once per mesh: a 16-byte header and one 48-byte record per face (corners and state), padded with zeros to
+ *   whole chunks; after it nothing reads verts_dev or faces_dev again.  info_dev (optional) int32[ASDF_MESH_SDF_INFO_WORDS]:
+ *   [ASDF_MESH_SDF_INFO_SKIPPED] absent faces, [ASDF_MESH_SDF_INFO_ZERO_AREA] zero-area faces, rest 0.  workspace_dev 16-byte aligned.
+ * asdf_mesh_sdf_points: sdf_dev [M], winding_dev [M], face_dev [M], closest_dev [M][3]; each may be NULL and a NULL output leaves
+ *   the others exactly as they are (the winding sum is skipped when neither sdf nor winding is asked for).  One query per lane; a
+ *   wave stages ASDF_MESH_SDF_BLOCK_FACES records at a time into LDS.  Two launch shapes with the same bits: every wave walks all
+ *   chunks itself, or - few queries - the second grid dimension splits the chunk range, partials go to scratch_dev and a second kernel
+ *   reduces them in chunk order.  The host picks the shape (a split needs at most ASDF_MESH_SDF_SPLIT_MAX_QUERIES queries and a bounded
+ *   scratch); the environment variable ASDF_MESH_SDF_SHAPE, read at every call, forces one for tests and measurements: "auto" (or
+ *   unset), "whole", "split" - a forced split that cannot be served and an unknown value are ASDF_EINVAL.  M == 0 and num_faces == 0 are
+ *   ASDF_OK.  ASDF_EINVAL: a negative size, num_faces above INT32_MAX - ASDF_MESH_SDF_CHUNK_FACES, a NULL or misaligned required
+ *   pointer. */
+#define ASDF_MESH_SDF_BLOCK_FACES 64
+#define ASDF_MESH_SDF_CHUNK_FACES 128
+#define ASDF_MESH_SDF_RECORD_BYTES 48
+#define ASDF_MESH_SDF_SPLIT_MAX_QUERIES 131072
+#define ASDF_MESH_SDF_INFO_SKIPPED 0
+#define ASDF_MESH_SDF_INFO_ZERO_AREA 1
+#define ASDF_MESH_SDF_INFO_WORDS 4
+#define ASDF_MESH_SDF_SHAPE_AUTO 0
+#define ASDF_MESH_SDF_SHAPE_WHOLE 1
+#define ASDF_MESH_SDF_SHAPE_SPLIT 2
+int asdf_mesh_sdf_workspace_bytes(int32_t num_faces, int64_t M, size_t* bytes);
+int asdf_mesh_sdf_prepare(const float* verts_dev, int32_t num_verts, const int32_t* faces_dev, int32_t num_faces, void* workspace_dev,
+                          int32_t* info_dev, void* stream);
+int asdf_mesh_sdf_points(const void* workspace_dev, int32_t num_faces, const float* xyz_dev, int64_t M, float* sdf_dev,
+                         float* winding_dev, int32_t* face_dev, float* closest_dev, void* scratch_dev, void* stream);
+
 /* ---- Translate + scale ICP of the reference's eval mode: ICP_T_S.run_icp_f (deep_sdf/metrics/icp_trans_scale.py:33-113),
  * called from utils/mesh.py:385-395.  src_dev [ns][3] are the ALREADY NORMALISED source samples (sample_mesh :25-31),
  * tgt_dev [nt][3] the target samples, both fp64 on the device.  Runs until the reference's stopping rules fire
