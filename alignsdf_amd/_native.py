@@ -41,7 +41,10 @@ EXPORTS = (
     "asdf_decode_points_vjp",
     # (the mesh signed distance unit, csrc/mesh_sdf.hip: looked up by name in the same way)
     "asdf_mesh_sdf_workspace_bytes", "asdf_mesh_sdf_prepare", "asdf_mesh_sdf_points",
+    # (the device-resident fit loop, csrc/decoder.hip: looked up by name in the same way)
+    "asdf_fit_code",
 )
+FIT_STATE_BYTES = 5120  # ASDF_FIT_STATE_BYTES
 MATH_F32, MATH_F16X3 = 0, 1
 MAX_CLASSES = 8
 
@@ -149,6 +152,7 @@ def lib():
     L.asdf_decode_points.argtypes = [vp, vp, i64, vp, vp, vp]
     L.asdf_decode_points_grad.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     L.asdf_decode_points_vjp.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.asdf_fit_code.argtypes = [vp, vp, i64, vp, i32, vp, i32, f32, vp, vp, f32, vp, i32, vp, ctypes.c_size_t, vp, vp]
     L.asdf_trace_rays.argtypes = [vp, vp, i64, vp] + [vp] * 8 + [vp]
     L.asdf_project_points.argtypes = [vp, vp, i64, i32, vp] + [vp] * 6 + [vp]
     L.asdf_decoder_set_classifier.argtypes = [vp, vp, vp, i32]

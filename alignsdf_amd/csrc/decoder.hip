@@ -988,6 +988,16 @@ int asdf_decode_points_grad(asdf_decoder_t* d, const float* xyz_dev, int64_t M, 
   return ASDF_OK;
 }
 
+// the reverse-mode scratch (first use; sized for the largest grid, so no call allocates after it): the workgroups' partial sums
+// [num_cus][kVjpFoldFloats], one d_fold block for callers that pass none, and the loss form's [num_cus][heads] fp64 sums
+static int vjp_scratch(asdf_decoder* d) {
+  if (d->vjp_partial) return ASDF_OK;
+  const size_t bytes = ((size_t)d->num_cus + 1) * kVjpFoldFloats * sizeof(float) + (size_t)d->num_cus * kHeads * sizeof(double);
+  const hipError_t e = hipMalloc((void**)&d->vjp_partial, bytes);
+  if (e != hipSuccess) { g_last_hip_error = (int)e; d->vjp_partial = nullptr; return e == hipErrorOutOfMemory ? ASDF_ENOMEM : ASDF_EHIP; }
+  return ASDF_OK;
+}
+
 int asdf_decode_points_vjp(asdf_decoder_t* d, const float* xyz_dev, int64_t M, const float* w_hand_dev, const float* w_obj_dev,
                            float* sdf_hand_dev, float* sdf_obj_dev, float* d_fold_dev, float* d_latent_dev, float* d_embed_dev, void* stream) {
   if (!d || M < 0 || (M > 0 && !xyz_dev)) return ASDF_EINVAL;
@@ -1002,10 +1012,7 @@ int asdf_decode_points_vjp(asdf_decoder_t* d, const float* xyz_dev, int64_t M, c
     if (d_embed_dev) ASDF_HIP(hipMemsetAsync(d_embed_dev, 0, (size_t)kHeads * ASDF_MAX_POINT_FEATS * 4 * sizeof(float), st));
     return ASDF_OK;
   }
-  if (!d->vjp_partial) {      // (first use; sized for the largest grid, so no call allocates after it)
-    const hipError_t e = hipMalloc((void**)&d->vjp_partial, ((size_t)d->num_cus + 1) * kVjpFoldFloats * sizeof(float));
-    if (e != hipSuccess) { g_last_hip_error = (int)e; d->vjp_partial = nullptr; return e == hipErrorOutOfMemory ? ASDF_ENOMEM : ASDF_EHIP; }
-  }
+  ASDF_TRY(vjp_scratch(d));
   // always the fp32 chain's weights and constants: d->math and the MFMA shape of the split-half sweeps are not looked at
   DecodeParams p;
   std::memset(&p, 0, sizeof(p));
@@ -1021,6 +1028,55 @@ int asdf_decode_points_vjp(asdf_decoder_t* d, const float* xyz_dev, int64_t M, c
   k1v_launch(p, v, grid, st);
   float* fold = d_fold_dev ? d_fold_dev : d->vjp_partial + (size_t)d->num_cus * kVjpFoldFloats;
   k1v_finish(d->vjp_partial, grid, heads_mask, fold, d->wlat, d->wpt, ASDF_MAX_POINT_FEATS, d_latent_dev, d_embed_dev, st);
+  ASDF_HIP(hipGetLastError());
+  return ASDF_OK;
+}
+
+int asdf_fit_code(asdf_decoder_t* d, const float* xyz_dev, int64_t M, const float* t_hand_dev, int32_t n_hand, const float* t_obj_dev,
+                  int32_t n_obj, float clamp, float* z_dev, const float* z0_dev, float prior, const float* step_table_dev, int32_t steps,
+                  void* state_dev, size_t state_bytes, double* history_dev, void* stream) {
+  if (!d || M < 0 || steps < 0 || n_hand < 0 || n_obj < 0 || (M > 0 && !xyz_dev)) return ASDF_EINVAL;
+  if (!d->sample_bound) return ASDF_EINVAL;
+  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound || !d->streamT) return ASDF_ENOGRAD;
+  if (steps == 0 || M == 0) return ASDF_OK;
+  if (!z_dev || !step_table_dev || !state_dev || state_bytes < ASDF_FIT_STATE_BYTES || ((uintptr_t)state_dev & 3)) return ASDF_EINVAL;
+  if (!(clamp > 0.0f) || !(prior >= 0.0f) || n_hand > M || n_obj > M) return ASDF_EINVAL;
+  // a head without targets, or with an empty set, is absent
+  const float* t[2] = {n_hand > 0 ? t_hand_dev : nullptr, n_obj > 0 ? t_obj_dev : nullptr};
+  const int heads_mask = (t[0] ? 1 : 0) | (t[1] ? 2 : 0);
+  hipStream_t st = (hipStream_t)stream;
+  ASDF_TRY(vjp_scratch(d));
+  float* state = static_cast<float*>(state_dev);
+  float* fold = d->vjp_partial + (size_t)d->num_cus * kVjpFoldFloats;
+  double* loss_partial = reinterpret_cast<double*>(d->vjp_partial + ((size_t)d->num_cus + 1) * kVjpFoldFloats);
+  const double inv_n[2] = {t[0] ? 1.0 / n_hand : 0.0, t[1] ? 1.0 / n_obj : 0.0};
+  DecodeParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.stream = d->stream; p.cst = d->cst;
+  p.xyz = xyz_dev; p.P = M; p.N = 1; p.mode = kPointList;
+  p.first_mlp = t[0] ? 0 : 1;
+  p.num_mlps = heads_mask == 3 ? 2 : 1;
+  p.pf = d->spec.point_feats[0];
+  VjpParams v;
+  v.streamT = d->streamT; v.w[0] = t[0]; v.w[1] = t[1]; v.partial = d->vjp_partial;
+  VjpLossParams q;
+  q.clamp = clamp; q.inv_n[0] = (float)inv_n[0]; q.inv_n[1] = (float)inv_n[1]; q.partial = loss_partial;
+  AdamRule rule;
+  rule.b1 = 0.9f; rule.b2 = 0.999f; rule.eps = 1e-8f; rule.k_prior = (float)(2.0 * (double)prior / kLatent);
+  const int grid = k1v_grid(M, d->num_cus);
+  k1v_adam_init(state, z_dev, z0_dev, st);
+  for (int k = 0; k < steps; ++k) {
+    ASDF_TRY(set_sample_fold(d, z_dev, st));
+    if (heads_mask) {
+      k1v_loss_launch(p, v, q, grid, st);
+      k1v_finish_loss(d->vjp_partial, loss_partial, grid, heads_mask, fold, d->wlat, d->wpt, ASDF_MAX_POINT_FEATS, state + 3 * kLatent,
+                      inv_n[0], inv_n[1], history_dev ? history_dev + k : nullptr, st);
+    } else if (history_dev) {
+      ASDF_HIP(hipMemsetAsync(history_dev + k, 0, sizeof(double), st));      // (no data term: only the prior moves the code)
+    }
+    k1v_adam_step(state, step_table_dev + 2 * (size_t)k, rule, z_dev, st);
+  }
+  ASDF_TRY(set_sample_fold(d, z_dev, st));
   ASDF_HIP(hipGetLastError());
   return ASDF_OK;
 }

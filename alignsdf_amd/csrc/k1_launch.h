@@ -62,6 +62,26 @@ void k1v_launch(const DecodeParams& p, const VjpParams& v, int grid, hipStream_t
 // d_fold -> d_latent [256] / d_embed [heads][max_pf][4] (each may be null)
 void k1v_finish(const float* partial, int grid, int heads_mask, float* d_fold, const float* wlat, const float* wpt, int max_pf,
                 float* d_latent, float* d_embed, hipStream_t st);
+// The LOSS form of the same kernel (asdf_fit_code): VjpParams::w holds per-point targets (NaN: the point is not in that head's set), the
+// weight is made in the kernel - the clamped-L1 term of fit.fit_sample, sdf_mlp_vjp_kernel.h - and the workgroups' fp64 sums of the
+// term go to `partial`.  k1v_finish_loss is k1v_finish for d_latent plus, when `history` is given,
+// *history = sum over the evaluated heads of (the partials in workgroup order) inv_n_d[head].
+struct VjpLossParams {
+  float clamp;          // +inf: unclamped
+  float inv_n[2];       // 1 / (points of the head's set), rounded once from double
+  double* partial;      // [grid][heads]
+};
+void k1v_loss_launch(const DecodeParams& p, const VjpParams& v, const VjpLossParams& q, int grid, hipStream_t st);
+void k1v_finish_loss(const float* partial, const double* loss_partial, int grid, int heads_mask, float* d_fold, const float* wlat,
+                     const float* wpt, int max_pf, float* d_latent, double inv_n_hand, double inv_n_obj, double* history, hipStream_t st);
+// One Adam step of asdf_fit_code on the latent code (one workgroup, a lane per entry), every operation one correctly rounded fp32
+// operation in the order of fit.adam_step_host:
+//   g = d_latent + k_prior (z - z0);  m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  z = z - a (m / (sqrt(v) s + eps))
+// state = [z | m | v | d_latent | z0][kLatent]; step = (a, s) of this step; z is also written to z_out (the next fold reads it).
+constexpr int kFitStateFloats = 5 * kLatent;
+struct AdamRule { float b1, b2, eps, k_prior; };
+void k1v_adam_init(float* state, const float* z, const float* z0, hipStream_t st);      // z, z0 (null: z) in; m = v = 0
+void k1v_adam_step(float* state, const float* step, AdamRule rule, float* z_out, hipStream_t st);
 // sphere tracing on the fp32 chain (k1t_kernels.hip): one ray per MFMA column, free columns refilled from a per-head queue;
 // SeparateDecoder, affine point features.  The rule: sdf_mlp_trace_kernel.h
 struct TraceRule {

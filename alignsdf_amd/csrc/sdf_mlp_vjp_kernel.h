@@ -42,6 +42,7 @@ constexpr int kVjpRowFloats = 4;                                         // (dA[
 constexpr int kVjpHeadFloats = 2 * kHidden * kVjpRowFloats;               // [layer 0 / layer 2][512][4] = 4096
 constexpr int kVjpFoldFloats = kHeads * kVjpHeadFloats;                   // d_fold of the C ABI
 constexpr int kVjpLdsBytes = kLdsBytes + kWaves * kVjpHeadFloats * 4;     // ring + constants + the waves' sum blocks = 158 752 B
+constexpr int kVjpLossLdsBytes = kVjpLdsBytes + kWaves * 8;               // ... + the waves' fp64 loss sums (the loss form)
 
 // (VjpParams, the extra pointers of this form - a kernel argument of its own beside DecodeParams: k1_launch.h)
 
@@ -151,15 +152,31 @@ __device__ __forceinline__ f32x16 mask_tile(const f32x16& acc, unsigned m, int h
   return d;
 }
 
+// The sum of a double over the 32 lanes of the caller's lane half, in every lane of it: the butterfly of half_sum on 64-bit values
+// (loss form only; the terms are fp32 values, so the fp64 sum of a list is exact far beyond any list length)
+__device__ __forceinline__ double half_sum_f64(double v) {
+#pragma unroll
+  for (int m = 1; m <= 16; m <<= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
 // p.mode == kPointList, affine point features (KP == 2), SeparateDecoder; p.sdf0 / p.sdf1 may be null.  The host evaluates a head only
 // when its weights v.w[head] are given.
-__device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const VjpParams& v) {
+// LOSS (the fit form, asdf_fit_code): v.w[head] holds per-point TARGETS t instead of weights, and the weight is formed where the value
+// f is: with c = q.clamp,  r = clip(f, -c, c) - clip(t, -c, c),  l = |r|,  w = (t is NaN or f < -c or f > c) ? 0 : sign(r) q.inv_n[head]
+// - the clamped-L1 term of fit.fit_sample and its autograd weight (sign(0) = 0, the clamp's mask inclusive as torch.clamp's backward).
+// A NaN target takes the point out of the head's set (l = 0, w = 0).  The l of a workgroup's points are added in fp64 (per tile: the
+// half's butterfly, then the wave's LDS word; the waves in wave order) into q.partial[workgroup][head].  Everything behind w is the
+// reverse phase of the weight form, the same text.
+template <bool LOSS>
+__device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const VjpParams& v, const VjpLossParams& q) {
   constexpr int KP = 2;
   using CL = CstLayout<KP>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* ring = smem;
   float* cst = smem + kLdsRingFloats;
   float* sums = cst + CL::kFloats;                       // [wave][layer 0 / 2][512][4]
+  double* lsum = reinterpret_cast<double*>(sums + kWaves * kVjpHeadFloats);      // [wave] (LOSS only: kVjpLossLdsBytes)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -184,6 +201,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
       const f32x4* src4 = reinterpret_cast<const f32x4*>(p.cst + (size_t)head * CL::kFloats);
       for (int i = tid; i < CL::kFloats / 4; i += 256) reinterpret_cast<f32x4*>(cst)[i] = src4[i];
       for (int i = tid; i < kWaves * kVjpHeadFloats / 4; i += 256) reinterpret_cast<f32x4*>(sums)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (LOSS) { if (tid < kWaves) lsum[tid] = 0.0; }
     }
     const float* fwd0 = p.stream + (size_t)head * kStagesHead * kStageFloats;
     const float* rev0 = v.streamT + (size_t)head * kStagesHead * kStageFloats;
@@ -204,7 +222,10 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
       const long long pi = tile * kWgPts + wave * kWavePts + (lane & 31);
       const bool valid = pi < npts;
       float x0 = 0.f, x1 = 0.f, x2 = 0.f, wp = 0.f;
-      if (valid) { x0 = p.xyz[pi * 3 + 0]; x1 = p.xyz[pi * 3 + 1]; x2 = p.xyz[pi * 3 + 2]; wp = wgt[pi]; }
+      if (valid) {
+        x0 = p.xyz[pi * 3 + 0]; x1 = p.xyz[pi * 3 + 1]; x2 = p.xyz[pi * 3 + 2];
+        if constexpr (!LOSS) wp = wgt[pi];                      // (the loss form reads its target where it is used)
+      }
       float bp[KP];
       bp[0] = half ? x1 : x0;
       bp[1] = half ? 0.0f : x2;
@@ -325,6 +346,19 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
           float* so = head == 0 ? p.sdf0 : p.sdf1;
           if (so) so[pi] = sdf;
         }
+        if constexpr (LOSS) {
+          // the loss term and its weight (both lane halves hold the point's value; half 0 counts it); a padding column is a point
+          // outside the set
+          float t = __int_as_float(0x7fc00000);
+          if (valid) t = wgt[pi];
+          const float c = q.clamp;
+          const bool in_set = t == t;
+          const float r = __fsub_rn(fminf(fmaxf(sdf, -c), c), fminf(fmaxf(t, -c), c));
+          const float sgn = r > 0.0f ? q.inv_n[head] : (r < 0.0f ? -q.inv_n[head] : 0.0f);
+          const double l = half_sum_f64(in_set && half == 0 ? (double)fabsf(r) : 0.0);
+          if (lane == 0) lsum[wave] += l;
+          wp = (!in_set || sdf < -c || sdf > c) ? 0.0f : sgn;
+        }
         // u = w (1 - s^2), the gradient kernel's form; 0 in a padding column (wp = 0 there)
         u = valid ? __fmul_rn(wp, __fsub_rn(1.0f, __fmul_rn(sdf, sdf))) : 0.0f;
       }
@@ -444,6 +478,14 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
 #pragma unroll
         for (int w = 1; w < kWaves; ++w) s = __fadd_rn(s, sums[w * kVjpHeadFloats + i]);
         out[i] = s;
+      }
+      if constexpr (LOSS) {
+        if (tid2 == 0) {
+          double s = lsum[0];
+#pragma unroll
+          for (int w = 1; w < kWaves; ++w) s += lsum[w];
+          q.partial[(size_t)blockIdx.x * kHeads + head] = s;
+        }
       }
     }
   }   // MLPs

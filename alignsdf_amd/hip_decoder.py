@@ -1403,6 +1403,70 @@ class HipSdfDecoder:
         _native.check(code, "asdf_decode_points_vjp")
         return SdfVjp(sh, so, d_latent, (d_embed[0, :self._pf[0]], d_embed[1, :self._pf[1]]), d_fold)
 
+    def fit_code_refusal(self):
+        """Why fit_code would refuse this decoder, or None: the coverage of the reverse-mode kernel (vjp_refusal)."""
+        return vjp_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
+
+    def fit_code(self, xyz, t_hand, t_obj, n_hand, n_obj, latent, z0=None, steps=800, lr=5e-3, decay=0.1, every=400, prior=1e-4,
+                 clamp=0.05):
+        """Auto-decode on the device (asdf_fit_code): `steps` Adam steps on the latent code against per-point SDF targets, enqueued
+        as one stream of launches - fold, the loss form of the reverse-mode kernel, its finish, the Adam step - with nothing read
+        back and no wait.  xyz [M, 3]; t_hand / t_obj [M] targets of each head (None: the head is left out), NaN where a point is
+        not in that head's set; n_hand / n_obj the number of non-NaN targets (the caller's count - the targets are not read back to
+        count them).  The loss is fit.fit_sample's clamped-L1 term per head plus prior mean((z - z0)^2) (z0 None: the start code);
+        the rate of step k is lr decay^(k // every) (fit.adam_step_table).  The point embedding is the one set_sample bound; only
+        the code moves.  Returns (latent [L], history [steps] fp64: the data term before each step) as device tensors; the decoder
+        is then bound to the fitted code.  The rule, operation by operation: fit.clamped_l1_rule and fit.adam_step_host - which
+        fit.fit_code_lockstep runs one step at a time, to the same bits.  NotImplementedError(reason) for a decoder
+        fit_code_refusal() does not cover."""
+        from .fit import adam_step_table
+        why = self.fit_code_refusal()
+        if why is not None:
+            raise NotImplementedError("the fit kernel does not cover this decoder: %s" % why)
+        if self._bound is None:
+            raise ValueError("fit_code: bind the sample (its point embedding) with set_sample first")
+        dev32 = lambda t: t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        xyz = dev32(xyz)
+        M, steps = xyz.shape[0], int(steps)
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError("xyz has shape %s, expected [M, 3]" % (tuple(xyz.shape),))
+        ts = []
+        for name, t in (("t_hand", t_hand), ("t_obj", t_obj)):
+            if t is not None:
+                t = dev32(t).reshape(-1)
+                if t.numel() != M:
+                    raise ValueError("%s has %d elements, expected %d" % (name, t.numel(), M))
+            ts.append(t)
+        z = dev32(latent).reshape(-1).clone()
+        if z.numel() != self.latent_size:
+            raise ValueError("latent has %d elements, expected %d" % (z.numel(), self.latent_size))
+        z0 = None if z0 is None else dev32(z0).reshape(-1)
+        history = torch.zeros(steps, dtype=torch.float64, device=self.device)
+        # the state buffer is this call's own (the caching allocator keeps it in stream order); the step table is cached per schedule
+        # AND stream: a call on another torch stream uploads its own, so no call reads a table whose upload it is not ordered behind
+        self._fit_state = torch.empty(_native.FIT_STATE_BYTES // 4, dtype=torch.float32, device=self.device)
+        if not hasattr(self, "_fit_tables"):
+            self._fit_tables = {}
+        key = (steps, float(lr), float(decay), int(every), torch.cuda.current_stream(self.device).cuda_stream)
+        if key not in self._fit_tables:      # (one upload per schedule, from pinned memory: nothing queued is waited for)
+            if len(self._fit_tables) >= 8:
+                self._fit_tables.clear()
+            table = torch.from_numpy(adam_step_table(steps, lr, decay, every)).reshape(-1)
+            self._fit_tables[key] = (table.pin_memory() if steps else table).to(self.device, non_blocking=True)
+        table = self._fit_tables[key]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            code = self._L.asdf_fit_code(self._h, xyz.data_ptr(), M, ptr(ts[0]), int(n_hand), ptr(ts[1]), int(n_obj), float(clamp),
+                                         z.data_ptr(), ptr(z0), float(prior), table.data_ptr(), steps, self._fit_state.data_ptr(),
+                                         _native.FIT_STATE_BYTES, history.data_ptr(), self._stream())
+        if code == _native.ENOGRAD:
+            raise NotImplementedError("the fit kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
+        _native.check(code, "asdf_fit_code")
+        if steps > 0 and M > 0:
+            self._bound = (z.reshape(1, -1), self._bound[1])
+            self._latent = z
+        return z, history
+
     def trace_refusal(self):
         """trace_refusal() of this decoder: why trace_rays would refuse, or None."""
         return trace_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))

@@ -304,6 +304,34 @@ int asdf_decode_points_vjp(asdf_decoder_t* dec, const float* xyz_dev, int64_t M,
                            float* sdf_hand_dev, float* sdf_obj_dev, float* d_fold_dev, float* d_latent_dev, float* d_embed_dev,
                            void* stream);
 
+/* Auto-decode on the device: `steps` Adam steps on the bound sample's latent code against per-point SDF targets, enqueued as one
+ * stream of launches - the call never waits for the device and reads nothing back.  The point embedding is the one the last
+ * asdf_decoder_set_sample* bound; only the code moves.  xyz_dev [M][3]; t_hand_dev / t_obj_dev [M] fp32 targets of each head, NaN = the
+ * point is not in that head's set; n_hand / n_obj = the caller's count of non-NaN targets (not checked: the targets are not read
+ * back).  A NULL target list, or a count of 0, leaves that head out.  The loss is fit.fit_sample's clamped-L1 term,
+ *   sum over heads of (1 / n_head) sum over the head's set of |clip(f, -clamp, clamp) - clip(t, -clamp, clamp)|  +  prior mean((z - z0)^2)
+ * (clamp > 0, +inf = unclamped; z0_dev [256] the prior's centre, NULL = the start code).  Per step k, in `stream` order:
+ *   1. the fold of asdf_decoder_set_sample from z_dev;
+ *   2. the LOSS form of the reverse-mode kernel (csrc/sdf_mlp_vjp_kernel.h): per point w = (t is NaN or f < -clamp or f > clamp) ? 0 :
+ *      sign(clip(f) - clip(t)) fp32(1 / n_head) - sign(0) = 0, the clamp's mask inclusive as torch.clamp's backward - and behind w the
+ *      reverse phase of asdf_decode_points_vjp; the workgroups' fp64 sums of the term;
+ *   3. asdf_decode_points_vjp's finish: d_latent, and history_dev[k] (may be NULL; fp64 [steps]) = the data term BEFORE step k;
+ *   4. one Adam step on z (one workgroup; every operation one correctly rounded fp32 operation in this order, b1 = 0.9, b2 = 0.999,
+ *      eps = 1e-8, k_prior = fp32(2 prior / 256), (a_k, s_k) = step_table_dev[k] - fp32 [steps][2], computed by the caller in double
+ *      and rounded once: a_k = lr_k / (1 - b1^(k+1)), s_k = 1 / sqrt(1 - b2^(k+1))):
+ *        g = d_latent + k_prior (z - z0);  m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  z = z - a_k (m / (sqrt(v) s_k + eps))
+ * and one more fold after the last step, so that the bound sample is the fitted code, which is also what z_dev [256] holds (in: the
+ * start).  state_dev: ASDF_FIT_STATE_BYTES of caller-owned device memory (z, m, v, d_latent, z0), 4-byte aligned, written by the call.
+ * No persistent kernel, no barrier between workgroups, no graph: separate launches.  Every sum is taken in a fixed order: the same
+ * call twice gives the same bits.  steps == 0 or M == 0: ASDF_OK, nothing is launched, z_dev stays.  Not re-entrant per decoder (the
+ * scratch of asdf_decode_points_vjp).  ASDF_EINVAL / ASDF_ENOGRAD as asdf_decode_points_vjp; ASDF_EINVAL also for steps < 0, a count
+ * < 0 or > M, clamp not > 0, prior < 0 and - with work to do - NULL z_dev / step_table_dev / state_dev or a state buffer too small.
+ * (Looked up by name like asdf_decode_points_vjp: asdf_version() stays 132.) */
+#define ASDF_FIT_STATE_BYTES 5120
+int asdf_fit_code(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, const float* t_hand_dev, int32_t n_hand, const float* t_obj_dev,
+                  int32_t n_obj, float clamp, float* z_dev, const float* z0_dev, float prior, const float* step_table_dev, int32_t steps,
+                  void* state_dev, size_t state_bytes, double* history_dev, void* stream);
+
 /* Sphere tracing: the first surface of each head along M ray segments, marched and refined inside one kernel (csrc/k1t_kernels.hip -
  * a ray per column of the fp32 MFMA chain; a column whose ray is done takes the next ray of a device queue).  No counterpart in the
  * reference (it only ever meshes).  rays_dev [M][8] fp32, 16-byte aligned: origin (3), direction (3, need not be a unit vector), t0, t1 -
