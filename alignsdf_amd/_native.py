@@ -43,6 +43,8 @@ EXPORTS = (
     "asdf_mesh_sdf_workspace_bytes", "asdf_mesh_sdf_prepare", "asdf_mesh_sdf_points",
     # (the device-resident fit loop, csrc/decoder.hip: looked up by name in the same way)
     "asdf_fit_code",
+    # (the same loop over a batch of samples, csrc/k1vb_kernels.hip: looked up by name in the same way)
+    "asdf_fit_codes_workspace_bytes", "asdf_fit_codes",
 )
 FIT_STATE_BYTES = 5120  # ASDF_FIT_STATE_BYTES
 MATH_F32, MATH_F16X3 = 0, 1
@@ -153,6 +155,9 @@ def lib():
     L.asdf_decode_points_grad.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     L.asdf_decode_points_vjp.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.asdf_fit_code.argtypes = [vp, vp, i64, vp, i32, vp, i32, f32, vp, vp, f32, vp, i32, vp, ctypes.c_size_t, vp, vp]
+    L.asdf_fit_codes_workspace_bytes.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_size_t)]
+    L.asdf_fit_codes.argtypes = [vp, i32, vp, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), vp, ctypes.POINTER(i32), f32, vp, vp, vp, f32, vp,
+                                 i32, vp, ctypes.c_size_t, vp, vp]
     L.asdf_trace_rays.argtypes = [vp, vp, i64, vp] + [vp] * 8 + [vp]
     L.asdf_project_points.argtypes = [vp, vp, i64, i32, vp] + [vp] * 6 + [vp]
     L.asdf_decoder_set_classifier.argtypes = [vp, vp, vp, i32]

@@ -3,7 +3,7 @@
     python -m alignsdf_amd.autodecode -e EXP -t obman --data_root data --out CODES
            [--poses DIR] [--init DIR] [--unit_m 1.0] [--centre x y z]
            [--steps 800 --lr 5e-3 --decay 0.1 --every 400 --prior 1e-4 --clamp 0.05]
-           [--near 12000 --uniform 4000 --seed 0] [--start N --end N]
+           [--near 12000 --uniform 4000 --seed 0] [--start N --end N] [--batch B]
 
 For every name with both <data_root>/<task>/test/mesh_hand/<name>.obj and mesh_obj/<name>.obj (gt_interaction.discover) the two
 meshes are mapped into the decoder's normalised space,
@@ -16,7 +16,8 @@ and written as CODES/<name>.npz with `latent` [1, 256] and the pose arrays of --
 code_sources.npz_code_source reads.  A pose-aligned decoder (PointFeatSize > 3, EncodeStyle not "nerf") is bound with the sample's
 kinematic embedding and needs --poses: without it the run ends before any work.  CODES/autodecode.json holds, per sample, the first and
 the last data term, the step count and the fields' `info`.  Per sample the host waits for the device once: when it reads the fitted
-code to write the file.
+code to write the file.  --batch B fits B samples at a time in ONE stream of launches (fit.fit_codes: every step's launches carry all
+B), with one wait per batch; the files and the records are those of --batch 1, byte for byte.
 """
 import argparse
 import json
@@ -79,7 +80,8 @@ def write_code(out_dir, name, latent, poses):
 
 
 class DeviceFitter:
-    """fit_one of run() on the GPU: meshes -> MeshFields in the decoder's frame -> sdf samples -> fit.fit_code."""
+    """fit_one of run() on the GPU: meshes -> MeshFields in the decoder's frame -> sdf samples -> fit.fit_code; fit_many: the same for a
+    batch of samples through fit.fit_codes."""
 
     def __init__(self, decoder_module, specs, unit_m=1.0, centre=(0.0, 0.0, 0.0), fit=None, sampling=None):
         self.module, self.specs, self.unit_m = decoder_module, specs, float(unit_m)
@@ -87,9 +89,9 @@ class DeviceFitter:
         self.fit = dict(FIT_DEFAULTS, **(fit or {}))
         self.sampling = dict(SAMPLE_DEFAULTS, **(sampling or {}))
 
-    def __call__(self, name, hand_path, obj_path, poses, start):
+    def _prepare(self, hand_path, obj_path, poses, start):
+        """One sample up to the fit: (decoder, fit.fit_code's / fit.fit_codes' item, the fields)."""
         import torch
-        from .fit import fit_code
         from .mesh_sdf import MeshField, sdf_samples
         from .surface_sampling import load_obj
         from .utils.utils import decoder_for, sample_embedding
@@ -106,32 +108,70 @@ class DeviceFitter:
             fields[part] = MeshField(to_decoder_frame(verts, self.unit_m, centre, specs["SdfScaleFactor"]), faces, device=dec.device)
             samples[part] = sdf_samples(fields[part], self.sampling["near"], self.sampling["uniform"], seed=self.sampling["seed"])
         embed = sample_embedding(specs, mano, obj, getattr(dec, "combined", False))
+        item = {"latent": torch.from_numpy(np.asarray(start, np.float32)), "embed": embed, "sdf_hand": samples.get("hand"),
+                "sdf_obj": samples.get("obj")}
+        return dec, item, fields
+
+    @staticmethod
+    def _record(packed, steps, fields):
+        return packed[:-2].astype(np.float32), {"first": float(packed[-2]), "last": float(packed[-1]), "steps": int(steps),
+                                                "mesh_info": {part: f.info for part, f in fields.items()}}
+
+    def __call__(self, name, hand_path, obj_path, poses, start):
+        import torch
+        from .fit import fit_code
+        dec, item, fields = self._prepare(hand_path, obj_path, poses, start)
         # (a decoder the fit kernel refuses - CombinedDecoder, NeRF-encoded features - is fitted by the same rule on the module path)
-        latent, history = fit_code(dec, torch.from_numpy(np.asarray(start, np.float32)), embed, sdf_hand=samples.get("hand"),
-                                   sdf_obj=samples.get("obj"), module=self.module, specs=specs, **self.fit)
+        latent, history = fit_code(dec, item["latent"], item["embed"], sdf_hand=item["sdf_hand"], sdf_obj=item["sdf_obj"],
+                                   module=self.module, specs=self.specs, **self.fit)
         # the one wait of the sample: the fitted code (and, with it, the two ends of the history)
         ends = history[[0, -1]] if history.numel() else history.new_zeros(2)
         packed = torch.cat([latent.reshape(-1).double(), ends]).cpu().numpy()
-        rec = {"first": float(packed[-2]), "last": float(packed[-1]), "steps": int(history.numel()),
-               "mesh_info": {part: f.info for part, f in fields.items()}}
-        return packed[:-2].astype(np.float32), rec
+        return self._record(packed, history.numel(), fields)
+
+    def fit_many(self, jobs):
+        """fit_batch of run(): jobs = [(name, hand_path, obj_path, poses, start), ...] -> [(latent [L], record), ...], the samples'
+        fits enqueued as one stream of launches (fit.fit_codes) and one wait for the whole batch.  Every result is __call__'s of that
+        job, bit for bit.  Samples that ended up on different evaluators are fitted one by one."""
+        import torch
+        from .fit import fit_codes
+        prepared = [self._prepare(hand_path, obj_path, poses, start) for _, hand_path, obj_path, poses, start in jobs]
+        if any(dec is not prepared[0][0] for dec, _, _ in prepared):
+            return [self(*job) for job in jobs]
+        latents, history = fit_codes(prepared[0][0], [item for _, item, _ in prepared], module=self.module, specs=self.specs, **self.fit)
+        # the one wait of the batch: the fitted codes (and, with them, the two ends of each history)
+        steps = history.shape[1]
+        ends = history[:, [0, -1]] if steps else history.new_zeros((len(jobs), 2))
+        packed = torch.cat([latents.double(), ends], 1).cpu().numpy()
+        return [self._record(packed[s], steps, fields) for s, (_, _, fields) in enumerate(prepared)]
 
 
-def run(specs, fit_one, task, data_root, out_dir, poses_dir=None, init_dir=None, start=None, end=None):
+def run(specs, fit_one, task, data_root, out_dir, poses_dir=None, init_dir=None, start=None, end=None, batch=1):
     """The flow around `fit_one(name, hand_path, obj_path, poses, start_code) -> (latent [L], record)`: discovery, the [start, end)
-    range of the sorted pairs, the codes and autodecode.json.  ValueError before any work for a pose-aligned decoder without poses.
+    range of the sorted pairs, the codes and autodecode.json.  batch > 1: the pairs go, in order, in groups of `batch` (the last one
+    short) to `fit_one.fit_many([(name, hand_path, obj_path, poses, start_code), ...]) -> [(latent, record), ...]`; the files and the
+    records are those of batch == 1, in the same order.  ValueError before any work for a pose-aligned decoder without poses.
     Returns (json path, records)."""
     if pose_aligned(specs) and poses_dir is None:
         raise ValueError("a pose-aligned decoder (PointFeatSize %d, EncodeStyle %r) is fitted under the sample's pose: pass --poses <dir of "
                          "<name>.npz with global_trans, rot_center and obj_trans>" % (specs["PointFeatSize"], specs["EncodeStyle"]))
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch %d: at least 1" % batch)
     pairs = discover(data_root, task)[(None if start is None else int(start)):(None if end is None else int(end))]
     os.makedirs(out_dir, exist_ok=True)
     records = []
-    for name, hand_path, obj_path in pairs:
-        poses = load_poses(poses_dir, name, require_all=pose_aligned(specs))
-        latent, rec = fit_one(name, hand_path, obj_path, poses, load_init(init_dir, name, int(specs.get("LatentSize", 256))))
-        write_code(out_dir, name, latent, poses)
-        records.append(dict({"name": name}, **rec))
+    for at in range(0, len(pairs), batch):
+        jobs = []
+        for name, hand_path, obj_path in pairs[at:at + batch]:
+            poses = load_poses(poses_dir, name, require_all=pose_aligned(specs))
+            jobs.append((name, hand_path, obj_path, poses, load_init(init_dir, name, int(specs.get("LatentSize", 256)))))
+        results = [fit_one(*jobs[0])] if batch == 1 else fit_one.fit_many(jobs)
+        if len(results) != len(jobs):
+            raise RuntimeError("fit_many returned %d results for %d samples" % (len(results), len(jobs)))
+        for (name, _, _, poses, _), (latent, rec) in zip(jobs, results):
+            write_code(out_dir, name, latent, poses)
+            records.append(dict({"name": name}, **rec))
     path = os.path.join(out_dir, "autodecode.json")
     with open(path, "w") as f:
         json.dump({"task": task, "samples": records}, f, indent=1)
@@ -161,13 +201,14 @@ def main(argv=None):
         p.add_argument("--" + k, type=type(v), default=v)
     p.add_argument("--start", type=int, default=None)
     p.add_argument("--end", type=int, default=None)
+    p.add_argument("--batch", type=int, default=1, help="samples fitted in one stream of launches (default 1: one after the other)")
     a = p.parse_args(argv)
     from .reconstruct import load_experiment
     specs, module = load_experiment(a.experiment)
     if pose_aligned(specs) and a.poses is None:
         p.error("a pose-aligned decoder needs --poses")
     fitter = DeviceFitter(module, specs, a.unit_m, a.centre, {k: getattr(a, k) for k in FIT_DEFAULTS}, {k: getattr(a, k) for k in SAMPLE_DEFAULTS})
-    path, records = run(specs, fitter, a.task, a.data_root, a.out, a.poses, a.init, a.start, a.end)
+    path, records = run(specs, fitter, a.task, a.data_root, a.out, a.poses, a.init, a.start, a.end, a.batch)
     print(summary_line(records))
     print(path)
 

@@ -645,6 +645,7 @@ int asdf_decoder_create(const asdf_decoder_spec_t* spec, const asdf_head_params_
   if (e == hipSuccess) e = k1t_prepare();
   if (e == hipSuccess) e = k1p_prepare();
   if (e == hipSuccess) e = k1v_prepare();
+  if (e == hipSuccess) e = k1vb_prepare();
   if (e == hipSuccess) e = hipMalloc((void**)&d->trace_queue, 2 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc((void**)&d->latent_stage, kLatent * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&d->status, ASDF_STATUS_WORDS * sizeof(int));
@@ -1077,6 +1078,113 @@ int asdf_fit_code(asdf_decoder_t* d, const float* xyz_dev, int64_t M, const floa
     k1v_adam_step(state, step_table_dev + 2 * (size_t)k, rule, z_dev, st);
   }
   ASDF_TRY(set_sample_fold(d, z_dev, st));
+  ASDF_HIP(hipGetLastError());
+  return ASDF_OK;
+}
+
+// asdf_fit_codes' workspace, every part 256-byte aligned: [descriptors | workgroup map | constants blocks | partial sums | d_fold |
+// loss partials | Adam states].  ASDF_EINVAL where the batch cannot be described (the descriptors' words are 32-bit).
+struct FitCodesLayout {
+  size_t samples, wgs, cst, partial, fold, loss, state, bytes;
+  int total_wgs;
+};
+static int fit_codes_layout(const asdf_decoder* d, int32_t B, const int64_t* m, FitCodesLayout* L) {
+  if (!d || !m || !L || B < 1 || B > 65535) return ASDF_EINVAL;
+  long long pts = 0, wgs = 0;
+  for (int s = 0; s < B; ++s) {
+    if (m[s] < 1 || m[s] > INT32_MAX) return ASDF_EINVAL;
+    pts += m[s];
+    wgs += k1v_grid(m[s], d->num_cus);
+  }
+  if (pts > INT32_MAX || wgs > INT32_MAX) return ASDF_EINVAL;
+  size_t at = 0;
+  auto part = [&](size_t bytes) { const size_t here = at; at += (bytes + 255) & ~(size_t)255; return here; };
+  L->samples = part((size_t)B * sizeof(FitSampleDesc));
+  L->wgs = part((size_t)wgs * sizeof(FitWg));
+  L->cst = part((size_t)B * kHeads * kCstFloats * sizeof(float));
+  L->partial = part((size_t)wgs * kVjpFoldFloats * sizeof(float));
+  L->fold = part((size_t)B * kVjpFoldFloats * sizeof(float));
+  L->loss = part((size_t)wgs * kHeads * sizeof(double));
+  L->state = part((size_t)B * kFitStateFloats * sizeof(float));
+  L->bytes = at;
+  L->total_wgs = (int)wgs;
+  return ASDF_OK;
+}
+
+int asdf_fit_codes_workspace_bytes(const asdf_decoder_t* d, int32_t B, const int64_t* m, size_t* bytes) {
+  if (!bytes) return ASDF_EINVAL;
+  FitCodesLayout L;
+  ASDF_TRY(fit_codes_layout(d, B, m, &L));
+  *bytes = L.bytes;
+  return ASDF_OK;
+}
+
+int asdf_fit_codes(asdf_decoder_t* d, int32_t B, const float* xyz_dev, const int64_t* m, const float* t_hand_dev, const int32_t* n_hand,
+                   const float* t_obj_dev, const int32_t* n_obj, float clamp, float* z_dev, const float* z0_dev, const float* embed_dev,
+                   float prior, const float* step_table_dev, int32_t steps, void* workspace_dev, size_t workspace_bytes,
+                   double* history_dev, void* stream) {
+  if (!d || B < 1 || steps < 0 || !m || !xyz_dev) return ASDF_EINVAL;
+  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound || !d->streamT) return ASDF_ENOGRAD;
+  if (steps == 0) return ASDF_OK;
+  if (!z_dev || !embed_dev || !step_table_dev || !workspace_dev || ((uintptr_t)workspace_dev & 15)) return ASDF_EINVAL;
+  if (!(clamp > 0.0f) || !(prior >= 0.0f) || (t_hand_dev && !n_hand) || (t_obj_dev && !n_obj)) return ASDF_EINVAL;
+  FitCodesLayout L;
+  ASDF_TRY(fit_codes_layout(d, B, m, &L));
+  if (workspace_bytes < L.bytes) return ASDF_EINVAL;
+  // the descriptors: a head without targets, or with an empty set, is absent from its sample
+  std::vector<FitSampleDesc> descs((size_t)B);
+  int first = 0, wg0 = 0;
+  for (int s = 0; s < B; ++s) {
+    const int64_t nh = t_hand_dev ? n_hand[s] : 0, no = t_obj_dev ? n_obj[s] : 0;
+    if (nh < 0 || no < 0 || nh > m[s] || no > m[s] || (nh == 0 && no == 0)) return ASDF_EINVAL;
+    FitSampleDesc& sd = descs[(size_t)s];
+    std::memset(&sd, 0, sizeof(sd));
+    sd.first = first; sd.m = (int)m[s]; sd.grid = k1v_grid(m[s], d->num_cus); sd.wg0 = wg0;
+    sd.heads_mask = (nh > 0 ? 1 : 0) | (no > 0 ? 2 : 0);
+    sd.inv_n_d[0] = nh > 0 ? 1.0 / (double)nh : 0.0; sd.inv_n_d[1] = no > 0 ? 1.0 / (double)no : 0.0;
+    sd.inv_n[0] = (float)sd.inv_n_d[0]; sd.inv_n[1] = (float)sd.inv_n_d[1];
+    first += sd.m; wg0 += sd.grid;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace_dev);
+  FitSampleDesc* samples = reinterpret_cast<FitSampleDesc*>(ws + L.samples);
+  FitWg* wgs = reinterpret_cast<FitWg*>(ws + L.wgs);
+  float* cst_all = reinterpret_cast<float*>(ws + L.cst);
+  float* partial = reinterpret_cast<float*>(ws + L.partial);
+  float* fold = reinterpret_cast<float*>(ws + L.fold);
+  double* loss_partial = reinterpret_cast<double*>(ws + L.loss);
+  float* state = reinterpret_cast<float*>(ws + L.state);
+  // the fp32 chain's weights; the constants come from the workspace, so neither the bound sample nor any image of the decoder is touched
+  DecodeParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.stream = d->stream; p.cst = cst_all;
+  p.xyz = xyz_dev; p.P = 0; p.N = 1; p.mode = kPointList;
+  p.pf = d->spec.point_feats[0];
+  VjpParams v;
+  v.streamT = d->streamT; v.w[0] = t_hand_dev; v.w[1] = t_obj_dev; v.partial = partial;
+  VjpLossParams q;
+  q.clamp = clamp; q.inv_n[0] = q.inv_n[1] = 0.0f; q.partial = loss_partial;
+  VjpBatchParams b;
+  b.samples = samples; b.wgs = wgs; b.cst = cst_all;
+  AdamRule rule;
+  rule.b1 = 0.9f; rule.b2 = 0.999f; rule.eps = 1e-8f; rule.k_prior = (float)(2.0 * (double)prior / kLatent);
+  FoldParams fp;
+  std::memset(&fp, 0, sizeof(fp));
+  fp.wlat = d->wlat; fp.wpt = d->wpt; fp.bias02 = d->bias02; fp.kp = d->kp;
+  for (int h = 0; h < kHeads; ++h) {
+    fp.pf[h] = d->spec.point_feats[h];
+    for (int i = 0; i < 3; ++i) { fp.s2[i][h] = 1.0f; fp.s0[i][h] = 1.0f; }
+  }
+  k1vb_describe(descs.data(), B, samples, wgs, st);
+  k1vb_cst_init(d->cst, cst_all, B, st);
+  k1vb_adam_init(state, z_dev, z0_dev, B, st);
+  for (int k = 0; k < steps; ++k) {
+    k1vb_fold(fp, z_dev, embed_dev, cst_all, B, st);
+    k1vb_loss_launch(p, v, q, b, L.total_wgs, st);
+    k1vb_finish_loss(samples, B, partial, loss_partial, fold, d->wlat, d->wpt, ASDF_MAX_POINT_FEATS, state,
+                     history_dev ? history_dev + k : nullptr, steps, st);
+    k1vb_adam_step(state, step_table_dev + 2 * (size_t)k, rule, z_dev, B, st);
+  }
   ASDF_HIP(hipGetLastError());
   return ASDF_OK;
 }

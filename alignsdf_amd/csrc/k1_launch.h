@@ -82,6 +82,43 @@ constexpr int kFitStateFloats = 5 * kLatent;
 struct AdamRule { float b1, b2, eps, k_prior; };
 void k1v_adam_init(float* state, const float* z, const float* z0, hipStream_t st);      // z, z0 (null: z) in; m = v = 0
 void k1v_adam_step(float* state, const float* step, AdamRule rule, float* z_out, hipStream_t st);
+// The same stream of launches over a BATCH of samples (asdf_fit_codes, k1vb_kernels.hip): every sample has its own point list, targets,
+// code, embedding, constants block, partial sums and Adam state, and inside a sample everything is as above - sample s runs
+// grid_s = k1v_grid(m_s, num_cus) workgroups, workgroup g of it takes tiles g, g + grid_s, ... of its list, and every sum keeps its
+// order - so a sample's bits do not depend on its company.  The launch of the loss form has sum_s grid_s workgroups.
+struct FitSampleDesc {     // device-resident, read-only to the step's kernels
+  int first;               // the sample's first point in the concatenated lists
+  int m;                   // its points
+  int grid;                // its workgroups: k1v_grid(m, num_cus)
+  int wg0;                 // its first workgroup in the launch = its first row of the partial sums
+  int heads_mask;          // bit h: head h has targets in this sample
+  float inv_n[2];          // 1 / (points of the head's set), rounded once from double
+  int pad;
+  double inv_n_d[2];       // ... and in double, for the history
+};
+struct FitWg { int sample, g; };      // workgroup of the launch -> (sample, workgroup of the sample)
+struct VjpBatchParams {
+  const FitSampleDesc* samples;   // [B]
+  const FitWg* wgs;               // [sum of grids]
+  const float* cst;               // [B][heads][CstLayout<2>::kFloats]: the samples' fp32 constants images
+};
+constexpr int kFitDescChunk = 16;     // descriptors one k1vb_describe launch carries in its arguments
+struct FitDescChunk { int s0, count; FitSampleDesc d[kFitDescChunk]; };
+struct FoldParams;
+hipError_t k1vb_prepare();
+// descriptors and the workgroup map from the host's values, written by a kernel in stream order (no copy, nothing the host must keep)
+void k1vb_describe(const FitSampleDesc* host, int B, FitSampleDesc* samples, FitWg* wgs, hipStream_t st);
+// the static part of the fp32 constants image into every sample's block (the fold writes the rest)
+void k1vb_cst_init(const float* cst_src, float* cst_all, int B, hipStream_t st);
+// fold_sample_kernel's arithmetic for image 0 of fp (its scales, weights and point-feature counts), from z [B][256] and
+// embed [B][heads][ASDF_MAX_POINT_FEATS][4], into block s of cst_all
+void k1vb_fold(const FoldParams& fp, const float* z, const float* embed, float* cst_all, int B, hipStream_t st);
+void k1vb_loss_launch(const DecodeParams& p, const VjpParams& v, const VjpLossParams& q, const VjpBatchParams& b, int total_wgs, hipStream_t st);
+// per sample: partial -> d_fold[s], d_fold[s] -> d_latent (state[s] + 3 kLatent), and history[s * history_stride] when history is given
+void k1vb_finish_loss(const FitSampleDesc* samples, int B, const float* partial, const double* loss_partial, float* d_fold, const float* wlat,
+                      const float* wpt, int max_pf, float* state, double* history, long long history_stride, hipStream_t st);
+void k1vb_adam_init(float* state, const float* z, const float* z0, int B, hipStream_t st);      // z, z0 [B][256] (z0 null: z)
+void k1vb_adam_step(float* state, const float* step, AdamRule rule, float* z_out, int B, hipStream_t st);
 // sphere tracing on the fp32 chain (k1t_kernels.hip): one ray per MFMA column, free columns refilled from a per-head queue;
 // SeparateDecoder, affine point features.  The rule: sdf_mlp_trace_kernel.h
 struct TraceRule {

@@ -47,14 +47,7 @@ void k1v_finish(const float* partial, int grid, int heads_mask, float* d_fold, c
 __global__ void vjp_loss_reduce_kernel(const double* __restrict__ loss_partial, int grid, int heads_mask, double inv_n0, double inv_n1,
                                        double* __restrict__ history) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  double total = 0.0;
-  for (int head = 0; head < kHeads; ++head) {
-    if (!((heads_mask >> head) & 1)) continue;
-    double s = 0.0;
-    for (int g = 0; g < grid; ++g) s += loss_partial[(size_t)g * kHeads + head];
-    total += s * (head == 0 ? inv_n0 : inv_n1);
-  }
-  *history = total;
+  vjp_loss_total(loss_partial, grid, heads_mask, inv_n0, inv_n1, history);
 }
 
 void k1v_finish_loss(const float* partial, const double* loss_partial, int grid, int heads_mask, float* d_fold, const float* wlat,
@@ -64,35 +57,14 @@ void k1v_finish_loss(const float* partial, const double* loss_partial, int grid,
     hipLaunchKernelGGL(vjp_loss_reduce_kernel, dim3(1), dim3(64), 0, st, loss_partial, grid, heads_mask, inv_n_hand, inv_n_obj, history);
 }
 
+// (the Adam state's start and step: adam_init_body / adam_step_body of sdf_mlp_vjp_kernel.h, shared with the batched forms)
 __global__ __launch_bounds__(256) void adam_init_kernel(float* __restrict__ state, const float* __restrict__ z, const float* __restrict__ z0) {
-  const int i = threadIdx.x;
-  if (i >= kLatent) return;
-  const float zi = z[i];
-  state[i] = zi;
-  state[kLatent + i] = 0.0f;
-  state[2 * kLatent + i] = 0.0f;
-  state[3 * kLatent + i] = 0.0f;
-  state[4 * kLatent + i] = z0 ? z0[i] : zi;
+  adam_init_body(state, z, z0);
 }
 
-// (sqrtf and the division below are the compiler's correctly rounded forms - the default of this toolchain for fp32, and what
-// fit.adam_step_host's numpy operations are; __fsqrt_rn maps to the approximate instruction here.  The unit is built without
-// contraction, so no product is fused into a sum.)
 __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ state, const float* __restrict__ step, const AdamRule r,
                                                         float* __restrict__ z_out) {
-  const int i = threadIdx.x;
-  if (i >= kLatent) return;
-  const float a = step[0], s = step[1];
-  float z = state[i], m = state[kLatent + i], v = state[2 * kLatent + i];
-  const float g = __fadd_rn(state[3 * kLatent + i], __fmul_rn(r.k_prior, __fsub_rn(z, state[4 * kLatent + i])));
-  m = __fadd_rn(__fmul_rn(r.b1, m), __fmul_rn(__fsub_rn(1.0f, r.b1), g));
-  v = __fadd_rn(__fmul_rn(r.b2, v), __fmul_rn(__fmul_rn(__fsub_rn(1.0f, r.b2), g), g));
-  const float den = __fadd_rn(__fmul_rn(sqrtf(v), s), r.eps);
-  z = __fsub_rn(z, __fmul_rn(a, m / den));
-  state[i] = z;
-  state[kLatent + i] = m;
-  state[2 * kLatent + i] = v;
-  z_out[i] = z;
+  adam_step_body(state, step, r, z_out);
 }
 
 void k1v_adam_init(float* state, const float* z, const float* z0, hipStream_t st) {

@@ -69,6 +69,13 @@ __device__ __forceinline__ f32x16 relu16m(f32x16 v, int hi, unsigned& m) {
   return v;
 }
 
+// a value / pointer that is the same in every lane, held in scalar registers
+__device__ __forceinline__ int uniform_i(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ const float* uniform_ptr(const float* q) {
+  const unsigned long long a = (unsigned long long)(size_t)q;
+  return reinterpret_cast<const float*>((size_t)(((unsigned long long)(unsigned)uniform_i((int)(a >> 32)) << 32) | (unsigned)uniform_i((int)a)));
+}
+
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
@@ -168,8 +175,16 @@ __device__ __forceinline__ double half_sum_f64(double v) {
 // A NaN target takes the point out of the head's set (l = 0, w = 0).  The l of a workgroup's points are added in fp64 (per tile: the
 // half's butterfly, then the wave's LDS word; the waves in wave order) into q.partial[workgroup][head].  Everything behind w is the
 // reverse phase of the weight form, the same text.
-template <bool LOSS>
-__device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const VjpParams& v, const VjpLossParams& q) {
+// BATCH (asdf_fit_codes, k1vb_kernels.hip): the launch carries several point lists.  The body depends on its launch only through the
+// workgroup's index and the launch's size, p.P / xyz / cst / first_mlp / num_mlps, v.w[] / partial and q.inv_n[] / partial;
+// sdf_mlp_vjp_batch_body below makes those for the workgroup's sample and hands in its index inside the sample (wg) and the sample's
+// own grid (nwg) - everything behind this line is then the one-list form, the same text.
+template <bool LOSS, bool BATCH = false>
+__device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const VjpParams& v, const VjpLossParams& q, unsigned batch_wg = 0,
+                                                 unsigned batch_nwg = 0) {
+  // (read where they are used, as the one-list form always has: made once up here, the launch's size lives across the tile loop)
+  auto wg = [&]() -> unsigned { if constexpr (BATCH) return batch_wg; else return blockIdx.x; };
+  auto nwg = [&]() -> unsigned { if constexpr (BATCH) return batch_nwg; else return gridDim.x; };
   constexpr int KP = 2;
   using CL = CstLayout<KP>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -186,7 +201,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
 
   const long long npts = p.P;
   const long long ntiles = (npts + kWgPts - 1) / kWgPts;
-  if ((long long)blockIdx.x >= ntiles) return;           // (never: k1v_grid launches at most one workgroup per tile)
+  if ((long long)wg() >= ntiles) return;                 // (never: k1v_grid launches at most one workgroup per tile)
 
   const unsigned lds_ring_base = (unsigned)(size_t)(__attribute__((address_space(3))) float*)ring;
 
@@ -194,7 +209,9 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
   for (int slot = 0; slot < p.num_mlps; ++slot) {
     const int head = p.first_mlp + slot;
     const float* hc = cst;
-    const float* wgt = v.w[head];
+    const float* wgt;
+    if constexpr (BATCH) wgt = head ? v.w[1] : v.w[0];      // (v and q are the workgroup's own copies there: no indexed reads of them)
+    else wgt = v.w[head];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     {
@@ -218,7 +235,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
     f32x4 a1 = (reinterpret_cast<const f32x4*>(ring) + lane)[64];
 
 #pragma unroll 1
-    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    for (long long tile = wg(); tile < ntiles; tile += nwg()) {
       const long long pi = tile * kWgPts + wave * kWavePts + (lane & 31);
       const bool valid = pi < npts;
       float x0 = 0.f, x1 = 0.f, x2 = 0.f, wp = 0.f;
@@ -233,6 +250,10 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
       // the bases are made opaque per tile so that the per-lane source addresses are not hoisted out of the tile loop (spills)
       const float* fbase = fwd0;
       const float* rbase = rev0;
+      if constexpr (BATCH) {      // (derived from descriptor words: named uniform where the constraint below needs a scalar)
+        fbase = uniform_ptr(fbase);
+        rbase = uniform_ptr(rbase);
+      }
       asm volatile("" : "+s"(fbase));
       asm volatile("" : "+s"(rbase));
       auto src_of = [&](int s) -> const float* {   // s = stage index within the tile + 3
@@ -354,7 +375,8 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
           const float c = q.clamp;
           const bool in_set = t == t;
           const float r = __fsub_rn(fminf(fmaxf(sdf, -c), c), fminf(fmaxf(t, -c), c));
-          const float sgn = r > 0.0f ? q.inv_n[head] : (r < 0.0f ? -q.inv_n[head] : 0.0f);
+          auto inv_n = [&]() -> float { if constexpr (BATCH) return head ? q.inv_n[1] : q.inv_n[0]; else return q.inv_n[head]; };
+          const float sgn = r > 0.0f ? inv_n() : (r < 0.0f ? -inv_n() : 0.0f);
           const double l = half_sum_f64(in_set && half == 0 ? (double)fabsf(r) : 0.0);
           if (lane == 0) lsum[wave] += l;
           wp = (!in_set || sdf < -c || sdf > c) ? 0.0f : sgn;
@@ -470,7 +492,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
     // the four waves' sums, in wave order, into this workgroup's partial of the head
     __syncthreads();
     {
-      float* out = v.partial + ((size_t)blockIdx.x * kHeads + head) * kVjpHeadFloats;
+      float* out = v.partial + ((size_t)wg() * kHeads + head) * kVjpHeadFloats;
       // (the thread index is made again from the lane count: kept, it is one more register live across the tile loop)
       const int tid2 = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
       for (int i = tid2; i < kVjpHeadFloats; i += 256) {
@@ -484,7 +506,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
           double s = lsum[0];
 #pragma unroll
           for (int w = 1; w < kWaves; ++w) s += lsum[w];
-          q.partial[(size_t)blockIdx.x * kHeads + head] = s;
+          q.partial[(size_t)wg() * kHeads + head] = s;
         }
       }
     }
@@ -492,11 +514,37 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// The batched loss form (asdf_fit_codes): workgroup blockIdx.x of the launch is workgroup b.wgs[blockIdx.x].g of sample
+// b.wgs[blockIdx.x].sample.  The two words and the sample's descriptor are read with uniform addresses and held in scalar registers
+// (nothing is written through them: descriptors are read-only to this kernel); p.xyz, v.w[] are the concatenated lists of the batch,
+// v.partial / q.partial the rows of the whole launch, and the sample's share of each starts at its first point / first workgroup.
+__device__ __forceinline__ void sdf_mlp_vjp_batch_body(const DecodeParams& p, const VjpParams& v, const VjpLossParams& q, const VjpBatchParams& b) {
+  using CL = CstLayout<2>;
+  const FitWg w = b.wgs[blockIdx.x];
+  const int s = uniform_i(w.sample), g = uniform_i(w.g);
+  const FitSampleDesc* sd = b.samples + s;
+  const long long first = uniform_i(sd->first);
+  const int m = uniform_i(sd->m), grid = uniform_i(sd->grid), wg0 = uniform_i(sd->wg0), mask = uniform_i(sd->heads_mask);
+  DecodeParams ps = p;
+  ps.P = m;
+  ps.xyz = p.xyz + first * 3;
+  ps.cst = b.cst + (size_t)s * kHeads * CL::kFloats;
+  ps.first_mlp = (mask & 1) ? 0 : 1;
+  ps.num_mlps = mask == 3 ? 2 : 1;
+  VjpParams vs = v;
+  vs.w[0] = v.w[0] + first;            // (a head outside the sample's mask is not evaluated: its list is never read)
+  vs.w[1] = v.w[1] + first;
+  vs.partial = v.partial + (size_t)wg0 * kVjpFoldFloats;
+  VjpLossParams qs = q;
+  qs.inv_n[0] = __int_as_float(uniform_i(__float_as_int(sd->inv_n[0])));
+  qs.inv_n[1] = __int_as_float(uniform_i(__float_as_int(sd->inv_n[1])));
+  qs.partial = q.partial + (size_t)wg0 * kHeads;
+  sdf_mlp_vjp_body<true, true>(ps, vs, qs, (unsigned)g, (unsigned)grid);
+}
+
 // d_fold [2 heads][2 layers][512][4] = the workgroups' partials added in workgroup order (fp64 accumulator); a head that was not
-// evaluated (bit `head` of heads_mask clear) is written with zeros.  One thread per entry.
-__global__ __launch_bounds__(256) void vjp_reduce_kernel(const float* __restrict__ partial, int grid, int heads_mask, float* __restrict__ d_fold) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= kVjpFoldFloats) return;
+// evaluated (bit `head` of heads_mask clear) is written with zeros.  One thread per entry: entry e of it.
+__device__ __forceinline__ void vjp_reduce_entry(const float* __restrict__ partial, int grid, int heads_mask, float* __restrict__ d_fold, int e) {
   const int head = e / kVjpHeadFloats;
   double s = 0.0;
   if ((heads_mask >> head) & 1)
@@ -504,20 +552,19 @@ __global__ __launch_bounds__(256) void vjp_reduce_kernel(const float* __restrict
   d_fold[e] = (float)s;
 }
 
-// The adjoint of fold_sample_kernel on d_fold (c = b + W_lat z + W_pt E[:, 3], A[:, d] = W_pt E[:, d]):
+// The adjoint of fold_sample_kernel on d_fold (c = b + W_lat z + W_pt E[:, 3], A[:, d] = W_pt E[:, d]), workgroup `blk` of it:
 //   d_latent[k]      = sum over (head, layer, row) of wlat[head][layer][row][k] dc[row]                      blocks [0, 64): 4 k each
 //   d_embed[h][f][d] = sum over (layer, row) of wpt[h][layer][row][f] (d < 3 ? dA[row][d] : dc[row])          blocks 64 + h MAXPF + f
 // fp64 accumulators; a thread's terms in index order, then a fixed tree over the 256 threads.  Either output may be null.
-__global__ __launch_bounds__(256) void vjp_adjoint_kernel(const float* __restrict__ d_fold, const float* __restrict__ wlat,
-                                                          const float* __restrict__ wpt, int max_pf, float* __restrict__ d_latent,
-                                                          float* __restrict__ d_embed) {
+__device__ __forceinline__ void vjp_adjoint_body(const float* __restrict__ d_fold, const float* __restrict__ wlat, const float* __restrict__ wpt,
+                                                 int max_pf, float* __restrict__ d_latent, float* __restrict__ d_embed, unsigned blk) {
   __shared__ double red[256][4];
   const int tid = threadIdx.x;
   double a[4] = {0.0, 0.0, 0.0, 0.0};
-  const bool lat = blockIdx.x < kLatent / 4;
+  const bool lat = blk < kLatent / 4;
   if (lat) {
     if (!d_latent) return;
-    const int k4 = blockIdx.x * 4;
+    const int k4 = blk * 4;
     for (int j = tid; j < kHeads * 2 * kHidden; j += 256) {
       const f32x4 w = *reinterpret_cast<const f32x4*>(wlat + (size_t)j * kLatent + k4);
       const double dc = (double)d_fold[j * kVjpRowFloats + 3];
@@ -526,7 +573,7 @@ __global__ __launch_bounds__(256) void vjp_adjoint_kernel(const float* __restric
     }
   } else {
     if (!d_embed) return;
-    const int hf = blockIdx.x - kLatent / 4, h = hf / max_pf, f = hf % max_pf;
+    const int hf = blk - kLatent / 4, h = hf / max_pf, f = hf % max_pf;
     for (int j = h * 2 * kHidden + tid; j < (h + 1) * 2 * kHidden; j += 256) {
       const double w = (double)wpt[(size_t)j * max_pf + f];
       const f32x4 dv = *reinterpret_cast<const f32x4*>(d_fold + j * kVjpRowFloats);
@@ -544,9 +591,69 @@ __global__ __launch_bounds__(256) void vjp_adjoint_kernel(const float* __restric
     __syncthreads();
   }
   if (tid < 4) {
-    if (lat) d_latent[blockIdx.x * 4 + tid] = (float)red[0][tid];
-    else d_embed[(size_t)(blockIdx.x - kLatent / 4) * 4 + tid] = (float)red[0][tid];
+    if (lat) d_latent[blk * 4 + tid] = (float)red[0][tid];
+    else d_embed[(size_t)(blk - kLatent / 4) * 4 + tid] = (float)red[0][tid];
   }
 }
+
+// The data term of one step: per evaluated head the workgroups' fp64 sums in workgroup order, times 1 / n of the head, hand first
+// (one thread).
+__device__ __forceinline__ void vjp_loss_total(const double* __restrict__ loss_partial, int grid, int heads_mask, double inv_n0, double inv_n1,
+                                               double* __restrict__ history) {
+  double total = 0.0;
+  for (int head = 0; head < kHeads; ++head) {
+    if (!((heads_mask >> head) & 1)) continue;
+    double s = 0.0;
+    for (int g = 0; g < grid; ++g) s += loss_partial[(size_t)g * kHeads + head];
+    total += s * (head == 0 ? inv_n0 : inv_n1);
+  }
+  *history = total;
+}
+
+// The Adam state of one code (k1_launch.h: [z | m | v | d_latent | z0][kLatent]), a lane per entry: its start ...
+__device__ __forceinline__ void adam_init_body(float* __restrict__ state, const float* __restrict__ z, const float* __restrict__ z0) {
+  const int i = threadIdx.x;
+  if (i >= kLatent) return;
+  const float zi = z[i];
+  state[i] = zi;
+  state[kLatent + i] = 0.0f;
+  state[2 * kLatent + i] = 0.0f;
+  state[3 * kLatent + i] = 0.0f;
+  state[4 * kLatent + i] = z0 ? z0[i] : zi;
+}
+
+// ... and one step.  (sqrtf and the division below are the compiler's correctly rounded forms - the default of this toolchain for fp32,
+// and what fit.adam_step_host's numpy operations are; __fsqrt_rn maps to the approximate instruction here.  The units are built without
+// contraction, so no product is fused into a sum.)
+__device__ __forceinline__ void adam_step_body(float* __restrict__ state, const float* __restrict__ step, const AdamRule& r, float* __restrict__ z_out) {
+  const int i = threadIdx.x;
+  if (i >= kLatent) return;
+  const float a = step[0], s = step[1];
+  float z = state[i], m = state[kLatent + i], v = state[2 * kLatent + i];
+  const float g = __fadd_rn(state[3 * kLatent + i], __fmul_rn(r.k_prior, __fsub_rn(z, state[4 * kLatent + i])));
+  m = __fadd_rn(__fmul_rn(r.b1, m), __fmul_rn(__fsub_rn(1.0f, r.b1), g));
+  v = __fadd_rn(__fmul_rn(r.b2, v), __fmul_rn(__fmul_rn(__fsub_rn(1.0f, r.b2), g), g));
+  const float den = __fadd_rn(__fmul_rn(sqrtf(v), s), r.eps);
+  z = __fsub_rn(z, __fmul_rn(a, m / den));
+  state[i] = z;
+  state[kLatent + i] = m;
+  state[2 * kLatent + i] = v;
+  z_out[i] = z;
+}
+
+// (the one-list kernels of these bodies; k1vb_kernels.hip, which has its own per-sample forms, leaves them out)
+#ifndef ASDF_VJP_BODIES_ONLY
+__global__ __launch_bounds__(256) void vjp_reduce_kernel(const float* __restrict__ partial, int grid, int heads_mask, float* __restrict__ d_fold) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= kVjpFoldFloats) return;
+  vjp_reduce_entry(partial, grid, heads_mask, d_fold, e);
+}
+
+__global__ __launch_bounds__(256) void vjp_adjoint_kernel(const float* __restrict__ d_fold, const float* __restrict__ wlat,
+                                                          const float* __restrict__ wpt, int max_pf, float* __restrict__ d_latent,
+                                                          float* __restrict__ d_embed) {
+  vjp_adjoint_body(d_fold, wlat, wpt, max_pf, d_latent, d_embed, blockIdx.x);
+}
+#endif
 
 }  // namespace asdf

@@ -391,3 +391,28 @@ def fit_code(decoder, latent, embed, sdf_hand=None, sdf_obj=None, surface_hand=N
         return fit_code_lockstep(fallback, latent, embed, xyz, t_hand, t_obj, n_hand, n_obj, **kw)
     _bind_code(decoder, latent, embed)
     return decoder.fit_code(xyz, t_hand, t_obj, n_hand, n_obj, latent, **kw)
+
+
+def fit_codes(decoder, items, steps=800, lr=5e-3, decay=0.1, every=400, prior=1e-4, clamp=0.05, module=None, specs=None):
+    """fit_code over many samples.  Each item is a dict with fit_code's per-sample inputs: `latent`, `embed` and any of `sdf_hand`,
+    `sdf_obj`, `surface_hand`, `surface_obj`, `z0` (absent = None); the rule (steps, lr, decay, every, prior, clamp) is shared.  On a
+    HipSdfDecoder the kernel covers, the whole batch is ONE stream of launches (HipSdfDecoder.fit_codes: every step carries all
+    samples, nothing is read back, nothing waits), every sample to the bits fit_code gives it alone; the decoder's bound sample is
+    left as it was.  On a TorchModuleDecoder - and, with `module` and `specs`, on a HipSdfDecoder the kernel refuses - the items run
+    through fit_code one after the other: the results of a loop over fit_code.  Returns (latents [B, L], history [B, steps] fp64),
+    device tensors."""
+    items = list(items)
+    if not items:
+        raise ValueError("fit_codes: no items")
+    rule = dict(steps=steps, lr=lr, decay=decay, every=every, prior=prior, clamp=clamp)
+    kinds = ("sdf_hand", "sdf_obj", "surface_hand", "surface_obj")
+    if hasattr(decoder, "decode_embedded") or decoder.fit_codes_refusal() is not None:
+        outs = [fit_code(decoder, it["latent"], it.get("embed"), z0=it.get("z0"), module=module, specs=specs,
+                         **{k: it.get(k) for k in kinds}, **rule) for it in items]
+        return torch.stack([z for z, _ in outs]), torch.stack([h for _, h in outs])
+    targets = [fit_targets(decoder, *(it.get(k) for k in kinds)) for it in items]
+    latents = torch.stack([it["latent"].detach().reshape(-1).to(decoder.device, torch.float32) for it in items])
+    z0s = [it.get("z0") for it in items]
+    return decoder.fit_codes([t[0] for t in targets], [t[1] for t in targets], [t[2] for t in targets], [t[3] for t in targets],
+                             [t[4] for t in targets], latents, [it.get("embed") for it in items],
+                             z0=None if all(c is None for c in z0s) else z0s, **rule)

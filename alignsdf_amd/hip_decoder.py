@@ -1419,7 +1419,6 @@ class HipSdfDecoder:
         is then bound to the fitted code.  The rule, operation by operation: fit.clamped_l1_rule and fit.adam_step_host - which
         fit.fit_code_lockstep runs one step at a time, to the same bits.  NotImplementedError(reason) for a decoder
         fit_code_refusal() does not cover."""
-        from .fit import adam_step_table
         why = self.fit_code_refusal()
         if why is not None:
             raise NotImplementedError("the fit kernel does not cover this decoder: %s" % why)
@@ -1445,15 +1444,7 @@ class HipSdfDecoder:
         # the state buffer is this call's own (the caching allocator keeps it in stream order); the step table is cached per schedule
         # AND stream: a call on another torch stream uploads its own, so no call reads a table whose upload it is not ordered behind
         self._fit_state = torch.empty(_native.FIT_STATE_BYTES // 4, dtype=torch.float32, device=self.device)
-        if not hasattr(self, "_fit_tables"):
-            self._fit_tables = {}
-        key = (steps, float(lr), float(decay), int(every), torch.cuda.current_stream(self.device).cuda_stream)
-        if key not in self._fit_tables:      # (one upload per schedule, from pinned memory: nothing queued is waited for)
-            if len(self._fit_tables) >= 8:
-                self._fit_tables.clear()
-            table = torch.from_numpy(adam_step_table(steps, lr, decay, every)).reshape(-1)
-            self._fit_tables[key] = (table.pin_memory() if steps else table).to(self.device, non_blocking=True)
-        table = self._fit_tables[key]
+        table = self._fit_table(steps, lr, decay, every)
         ptr = lambda t: t.data_ptr() if t is not None else None
         with torch.cuda.device(self.device):
             code = self._L.asdf_fit_code(self._h, xyz.data_ptr(), M, ptr(ts[0]), int(n_hand), ptr(ts[1]), int(n_obj), float(clamp),
@@ -1465,6 +1456,105 @@ class HipSdfDecoder:
         if steps > 0 and M > 0:
             self._bound = (z.reshape(1, -1), self._bound[1])
             self._latent = z
+        return z, history
+
+    def fit_codes_refusal(self):
+        """Why fit_codes would refuse this decoder, or None: fit_code_refusal()."""
+        return self.fit_code_refusal()
+
+    def _fit_table(self, steps, lr, decay, every):
+        """fit_code's cache of step tables on the device, per schedule and stream."""
+        from .fit import adam_step_table
+        if not hasattr(self, "_fit_tables"):
+            self._fit_tables = {}
+        key = (steps, float(lr), float(decay), int(every), torch.cuda.current_stream(self.device).cuda_stream)
+        if key not in self._fit_tables:      # (one upload per schedule, from pinned memory: nothing queued is waited for)
+            if len(self._fit_tables) >= 8:
+                self._fit_tables.clear()
+            table = torch.from_numpy(adam_step_table(steps, lr, decay, every)).reshape(-1)
+            self._fit_tables[key] = (table.pin_memory() if steps else table).to(self.device, non_blocking=True)
+        return self._fit_tables[key]
+
+    def fit_codes(self, xyz_list, t_hand_list, t_obj_list, n_hand, n_obj, latents, embeds, z0=None, steps=800, lr=5e-3, decay=0.1,
+                  every=400, prior=1e-4, clamp=0.05):
+        """fit_code over B samples in one stream of launches (asdf_fit_codes): every step's six launches carry all B samples, each with
+        its own points, targets, code, embedding, partial sums and Adam state, and every sample comes out with exactly the bits
+        fit_code gives it alone - at any position, in any company.  xyz_list[s] [m_s, 3]; t_hand_list[s] / t_obj_list[s] [m_s] or
+        None (the lists themselves may be None: no sample has that head), NaN where a point is not in the head's set; n_hand[s] /
+        n_obj[s] the counts of non-NaN targets; latents [B, L] the start codes; embeds[s] = (hand_E, obj_E) as set_sample takes them,
+        or None (plain xyz); z0 None, [B, L], or a list with None (= the start code) for some samples.  The schedule, the prior and the
+        clamp are shared.  Returns (latents [B, L], history [B, steps] fp64) as device tensors; nothing is read back and nothing
+        waits.  The decoder's bound sample, math mode and status are neither needed nor changed.  NotImplementedError(reason) for a
+        decoder fit_codes_refusal() does not cover."""
+        why = self.fit_codes_refusal()
+        if why is not None:
+            raise NotImplementedError("the fit kernel does not cover this decoder: %s" % why)
+        dev32 = lambda t: torch.as_tensor(t).detach().to(device=self.device, dtype=torch.float32).contiguous()
+        B, steps = len(xyz_list), int(steps)
+        if B < 1:
+            raise ValueError("fit_codes: an empty batch")
+        xs = [dev32(x) for x in xyz_list]
+        for x in xs:
+            if x.dim() != 2 or x.shape[1] != 3 or x.shape[0] < 1:
+                raise ValueError("xyz has shape %s, expected [m, 3] with m >= 1" % (tuple(x.shape),))
+        ms = [int(x.shape[0]) for x in xs]
+        ts, ns = [], []
+        for name, tl, nl in (("t_hand", t_hand_list, n_hand), ("t_obj", t_obj_list, n_obj)):
+            if tl is None or all(t is None for t in tl):
+                ts.append(None)
+                ns.append(None)
+                continue
+            if len(tl) != B or len(nl) != B:
+                raise ValueError("%s: %d lists and %d counts for %d samples" % (name, len(tl), len(nl), B))
+            parts = []
+            for s, t in enumerate(tl):
+                if t is None:
+                    parts.append(torch.full((ms[s],), float("nan"), dtype=torch.float32, device=self.device))
+                else:
+                    t = dev32(t).reshape(-1)
+                    if t.numel() != ms[s]:
+                        raise ValueError("%s of sample %d has %d elements, expected %d" % (name, s, t.numel(), ms[s]))
+                    parts.append(t)
+            ts.append(torch.cat(parts))
+            ns.append((ctypes.c_int32 * B)(*[0 if t is None else int(n) for t, n in zip(tl, nl)]))
+        xyz = torch.cat(xs, 0)
+        z = dev32(latents).reshape(B, -1).clone()
+        if z.shape[1] != self.latent_size:
+            raise ValueError("latents have %d elements each, expected %d" % (z.shape[1], self.latent_size))
+        if z0 is None:
+            z0t = None
+        elif torch.is_tensor(z0):
+            z0t = dev32(z0).reshape(B, self.latent_size)
+        else:       # (None = the sample's start code, which is also what a NULL z0 means for the whole batch)
+            z0t = torch.stack([z[s] if c is None else dev32(c).reshape(-1) for s, c in enumerate(z0)]).contiguous()
+        if len(embeds) != B:
+            raise ValueError("fit_codes: %d embeddings for %d samples" % (len(embeds), B))
+        emb = torch.zeros((B, 2, _native.MAX_POINT_FEATS, 4), dtype=torch.float32)
+        buf = emb.numpy()
+        for s, embed in enumerate(embeds):
+            if embed is None and any(f != 3 for f in self._pf):
+                raise ValueError("this decoder needs a point embedding (point features per head: %s)" % (self._pf,))
+            for h in range(2):
+                e = np.eye(3, 4) if embed is None else np.asarray(embed[h].detach().cpu() if torch.is_tensor(embed[h]) else embed[h], np.float64)
+                if e.shape != (self._pf[h], 4):
+                    raise ValueError("embedding of head %d of sample %d has shape %s, expected %s" % (h, s, e.shape, (self._pf[h], 4)))
+                buf[s, h, :self._pf[h]] = e.astype(np.float32)
+        emb = emb.pin_memory().to(self.device, non_blocking=True)
+        history = torch.zeros((B, steps), dtype=torch.float64, device=self.device)
+        table = self._fit_table(steps, lr, decay, every)
+        m_arr = (ctypes.c_int64 * B)(*ms)
+        nbytes = ctypes.c_size_t(0)
+        _native.check(self._L.asdf_fit_codes_workspace_bytes(self._h, B, m_arr, ctypes.byref(nbytes)), "asdf_fit_codes_workspace_bytes")
+        # (this call's own: the caching allocator keeps it in stream order, and two calls on two streams have one each)
+        workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            code = self._L.asdf_fit_codes(self._h, B, xyz.data_ptr(), m_arr, ptr(ts[0]), ns[0], ptr(ts[1]), ns[1], float(clamp), z.data_ptr(),
+                                          ptr(z0t), emb.data_ptr(), float(prior), table.data_ptr(), steps, workspace.data_ptr(), nbytes.value,
+                                          history.data_ptr(), self._stream())
+        if code == _native.ENOGRAD:
+            raise NotImplementedError("the fit kernel does not cover this decoder: %s" % self._L.asdf_strerror(code).decode())
+        _native.check(code, "asdf_fit_codes")
         return z, history
 
     def trace_refusal(self):

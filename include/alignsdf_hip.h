@@ -332,6 +332,32 @@ int asdf_fit_code(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, const fl
                   int32_t n_obj, float clamp, float* z_dev, const float* z0_dev, float prior, const float* step_table_dev, int32_t steps,
                   void* state_dev, size_t state_bytes, double* history_dev, void* stream);
 
+/* asdf_fit_code over a batch of B samples in ONE stream of launches: a step of the whole batch is the same six launches as a step of
+ * one sample (fold, the loss form of the reverse-mode kernel, reduce, adjoint, loss reduce, Adam), each carrying every sample - with
+ * its own point list, targets, code, embedding, constants block, partial sums and Adam state (csrc/k1vb_kernels.hip).  Inside a sample
+ * everything is asdf_fit_code's: the same workgroup count for its list, the same tiles per workgroup, every sum in the same order.  So
+ * z_dev[s] and history_dev[s] come out with exactly the bits asdf_fit_code gives that sample alone, at any position in any batch.
+ *   xyz_dev [sum m][3], t_hand_dev / t_obj_dev [sum m]: the samples' lists one behind the other, delimited by the HOST array m[B]
+ *   (each >= 1).  A NULL target list leaves that head out of the whole batch; n_hand[s] / n_obj[s] (host arrays, the counts of non-NaN
+ *   targets) == 0 leaves it out of sample s.  z_dev [B][256] in: the start codes, out: the fitted ones.  z0_dev [B][256] the priors'
+ *   centres, NULL = every sample's start code.  embed_dev [B][2][ASDF_MAX_POINT_FEATS][4]: the samples' point embeddings, in the
+ *   layout of asdf_decoder_set_sample.  step_table_dev [steps][2] as in asdf_fit_code, shared.  history_dev [B][steps] fp64, may be
+ *   NULL.  workspace_dev: asdf_fit_codes_workspace_bytes(dec, B, m) bytes of caller-owned device memory, 16-byte aligned.
+ * The call allocates no device memory, reads nothing back and never waits.  It neither needs nor changes the decoder's bound sample:
+ * it reads the decoder's weights only, writes none of its constants images, math mode or status word and uses none of its reverse-mode
+ * scratch - two batches with their own workspaces on two streams do not meet.  The launch of the loss form has sum over s of
+ * grid_s workgroups (grid_s = min(tiles of 128 points, compute units)); beyond the part's compute units they run in rounds.
+ * ASDF_ENOGRAD as asdf_fit_code.  ASDF_EINVAL: NULL decoder / xyz_dev / m, B < 1 or > 65535, steps < 0, and - with steps > 0 - NULL
+ * z_dev / embed_dev / step_table_dev / workspace_dev, a target list without its count array, m[s] < 1, a count < 0 or > m[s], a sample
+ * with no head that has targets, clamp not > 0, prior < 0, a workspace misaligned or too small, more than 2^31 - 1 points or
+ * workgroups in all.  steps == 0: ASDF_OK, nothing is launched or written.
+ * (Looked up by name like asdf_decode_points_vjp: asdf_version() stays 132.) */
+int asdf_fit_codes_workspace_bytes(const asdf_decoder_t* dec, int32_t B, const int64_t* m, size_t* bytes);   /* host only */
+int asdf_fit_codes(asdf_decoder_t* dec, int32_t B, const float* xyz_dev, const int64_t* m, const float* t_hand_dev, const int32_t* n_hand,
+                   const float* t_obj_dev, const int32_t* n_obj, float clamp, float* z_dev, const float* z0_dev, const float* embed_dev,
+                   float prior, const float* step_table_dev, int32_t steps, void* workspace_dev, size_t workspace_bytes,
+                   double* history_dev, void* stream);
+
 /* Sphere tracing: the first surface of each head along M ray segments, marched and refined inside one kernel (csrc/k1t_kernels.hip -
  * a ray per column of the fp32 MFMA chain; a column whose ray is done takes the next ray of a device queue).  No counterpart in the
  * reference (it only ever meshes).  rays_dev [M][8] fp32, 16-byte aligned: origin (3), direction (3, need not be a unit vector), t0, t1 -
