@@ -118,26 +118,18 @@ class DeviceFitter:
                                                 "mesh_info": {part: f.info for part, f in fields.items()}}
 
     def __call__(self, name, hand_path, obj_path, poses, start):
-        import torch
-        from .fit import fit_code
-        dec, item, fields = self._prepare(hand_path, obj_path, poses, start)
-        # (a decoder the fit kernel refuses - CombinedDecoder, NeRF-encoded features - is fitted by the same rule on the module path)
-        latent, history = fit_code(dec, item["latent"], item["embed"], sdf_hand=item["sdf_hand"], sdf_obj=item["sdf_obj"],
-                                   module=self.module, specs=self.specs, **self.fit)
-        # the one wait of the sample: the fitted code (and, with it, the two ends of the history)
-        ends = history[[0, -1]] if history.numel() else history.new_zeros(2)
-        packed = torch.cat([latent.reshape(-1).double(), ends]).cpu().numpy()
-        return self._record(packed, history.numel(), fields)
+        return self.fit_many([(name, hand_path, obj_path, poses, start)])[0]
 
     def fit_many(self, jobs):
         """fit_batch of run(): jobs = [(name, hand_path, obj_path, poses, start), ...] -> [(latent [L], record), ...], the samples'
-        fits enqueued as one stream of launches (fit.fit_codes) and one wait for the whole batch.  Every result is __call__'s of that
-        job, bit for bit.  Samples that ended up on different evaluators are fitted one by one."""
+        fits enqueued as one stream of launches (fit.fit_codes) and one wait for the whole batch.  Every result is that of the job
+        alone, bit for bit.  Samples that ended up on different evaluators are fitted one by one."""
         import torch
         from .fit import fit_codes
         prepared = [self._prepare(hand_path, obj_path, poses, start) for _, hand_path, obj_path, poses, start in jobs]
-        if any(dec is not prepared[0][0] for dec, _, _ in prepared):
+        if len(jobs) > 1 and any(dec is not prepared[0][0] for dec, _, _ in prepared):
             return [self(*job) for job in jobs]
+        # (a decoder the fit kernel refuses - CombinedDecoder, NeRF-encoded features - is fitted by the same rule on the module path)
         latents, history = fit_codes(prepared[0][0], [item for _, item, _ in prepared], module=self.module, specs=self.specs, **self.fit)
         # the one wait of the batch: the fitted codes (and, with them, the two ends of each history)
         steps = history.shape[1]

@@ -503,6 +503,83 @@ static int decode_grid_band_impl(asdf_decoder_t* d, int32_t N, const float* orig
   return ASDF_OK;
 }
 
+// What the point-list forms of the fp32 chain (gradient, reverse mode, fit, tracing, projection) cover: SeparateDecoder with affine point
+// features and an ordinary (per-sample constant) latent.  (The reverse-mode forms also need the transposed weight image, d->streamT.)
+static bool point_list_covered(const asdf_decoder* d) {
+  return d->spec.num_heads == 2 && d->spec.feature_mode == ASDF_FEATURES_AFFINE && d->kp == 2 && !d->pixel_bound;
+}
+
+// ... and their launch over M points at xyz (null: the kernel has its own positions) for the heads of heads_mask (bit h: head h), with the
+// constants block `cst`: always the fp32 chain's weights - d->math and the MFMA shape of the split-half sweeps are not looked at
+static DecodeParams point_list_params(const asdf_decoder* d, const float* cst, const float* xyz, int64_t M, int heads_mask) {
+  DecodeParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.stream = d->stream; p.cst = cst;
+  p.xyz = xyz; p.P = M; p.N = 1; p.mode = kPointList;
+  p.first_mlp = (heads_mask & 1) ? 0 : 1;
+  p.num_mlps = heads_mask == 3 ? 2 : 1;
+  p.pf = d->spec.point_feats[0];
+  return p;
+}
+
+// ---- the fit (k1_launch.h: THE FIT): one loop for asdf_fit_codes and its batch of one, asdf_fit_code --------------------------------------
+// sample `first .. first + m` of the concatenated lists, whose workgroups start at wg0 of the launch; nh / no = the sizes of its heads'
+// sets.  A head with an empty set is absent; a sample without heads has no workgroups (only the prior moves its code).
+static FitSampleDesc fit_describe(const asdf_decoder* d, int first, int64_t m, int wg0, int64_t nh, int64_t no) {
+  FitSampleDesc sd;
+  std::memset(&sd, 0, sizeof(sd));
+  sd.first = first; sd.m = (int)m; sd.wg0 = wg0;
+  sd.heads_mask = (nh > 0 ? 1 : 0) | (no > 0 ? 2 : 0);
+  sd.grid = sd.heads_mask ? k1v_grid(m, d->num_cus) : 0;
+  sd.inv_n_d[0] = nh > 0 ? 1.0 / (double)nh : 0.0; sd.inv_n_d[1] = no > 0 ? 1.0 / (double)no : 0.0;
+  sd.inv_n[0] = (float)sd.inv_n_d[0]; sd.inv_n[1] = (float)sd.inv_n_d[1];
+  return sd;
+}
+
+struct FitBuffers {          // device memory of a fit over B samples
+  FitSampleDesc* samples;    // [B] and
+  FitWg* wgs;                // [sum of grids]: written here from the host's descriptors
+  const float* cst;          // [B][heads][kCstFloats] the constants blocks `fold` writes
+  float* partial;            // [sum of grids][kVjpFoldFloats]
+  float* fold;               // [B][kVjpFoldFloats] d_fold
+  double* loss_partial;      // [sum of grids][heads]
+  float* state;              // [B][kFitStateFloats] the Adam states
+  const float* xyz;          // the samples' lists one behind the other, and
+  const float* t[2];         // their targets per head (null: no sample has that head)
+  float* z;                  // [B][kLatent] in: the start codes, out: the fitted ones
+  const float* z0;           // [B][kLatent] (null: the start codes)
+  const float* step_table;   // [steps][2]
+  double* history;           // [B][steps] (null: not wanted)
+};
+
+// `steps` steps on the B samples of descs; fold() -> ASDF_* brings the constants blocks up to z before each step's loss launch
+template <class F>
+static int fit_loop(asdf_decoder* d, const FitSampleDesc* descs, int B, const FitBuffers& b, float clamp, float prior, int steps, hipStream_t st,
+                    F fold) {
+  const int total_wgs = descs[B - 1].wg0 + descs[B - 1].grid;
+  // (each workgroup of the loss form takes P, first_mlp, num_mlps and inv_n from its sample's descriptor)
+  const DecodeParams p = point_list_params(d, b.cst, b.xyz, 0, 3);
+  VjpParams v;
+  v.streamT = d->streamT; v.w[0] = b.t[0]; v.w[1] = b.t[1]; v.partial = b.partial;
+  VjpLossParams q;
+  q.clamp = clamp; q.inv_n[0] = q.inv_n[1] = 0.0f; q.partial = b.loss_partial;
+  VjpBatchParams vb;
+  vb.samples = b.samples; vb.wgs = b.wgs; vb.cst = b.cst;
+  AdamRule rule;
+  rule.b1 = 0.9f; rule.b2 = 0.999f; rule.eps = 1e-8f; rule.k_prior = (float)(2.0 * (double)prior / kLatent);
+  k1vb_describe(descs, B, b.samples, b.wgs, st);
+  k1vb_adam_init(b.state, b.z, b.z0, B, st);
+  for (int k = 0; k < steps; ++k) {
+    ASDF_TRY(fold());
+    if (total_wgs > 0) k1vb_loss_launch(p, v, q, vb, total_wgs, st);
+    k1vb_finish_loss(b.samples, B, b.partial, b.loss_partial, b.fold, d->wlat, d->wpt, ASDF_MAX_POINT_FEATS, b.state,
+                     b.history ? b.history + k : nullptr, steps, st);
+    k1vb_adam_step(b.state, b.step_table + 2 * (size_t)k, rule, b.z, B, st);
+  }
+  ASDF_HIP(hipGetLastError());
+  return ASDF_OK;
+}
+
 extern "C" {
 
 int asdf_version(void) { return 132; }      // (asdf_project_points is an addition: no existing call changed)
@@ -969,19 +1046,12 @@ int asdf_decode_points_grad(asdf_decoder_t* d, const float* xyz_dev, int64_t M, 
                             float* sdf_obj_dev, float* grad_obj_dev, void* stream) {
   if (!d || M < 0 || (M > 0 && !xyz_dev)) return ASDF_EINVAL;
   if (!d->sample_bound) return ASDF_EINVAL;
-  // SeparateDecoder with affine point features and an ordinary (per-sample constant) latent
-  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound) return ASDF_ENOGRAD;
+  if (!point_list_covered(d)) return ASDF_ENOGRAD;
   const bool want0 = sdf_hand_dev || grad_hand_dev, want1 = sdf_obj_dev || grad_obj_dev;
   if (M == 0 || (!want0 && !want1)) return ASDF_OK;
   hipStream_t st = (hipStream_t)stream;
-  // always the fp32 chain's weights and constants: d->math and the MFMA shape of the split-half sweeps are not looked at
-  DecodeParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.stream = d->stream; p.cst = d->cst;
-  p.sdf0 = sdf_hand_dev; p.sdf1 = sdf_obj_dev; p.xyz = xyz_dev; p.P = M; p.N = 1; p.mode = kPointList;
-  p.first_mlp = want0 ? 0 : 1;
-  p.num_mlps = want0 && want1 ? 2 : 1;
-  p.pf = d->spec.point_feats[0];
+  DecodeParams p = point_list_params(d, d->cst, xyz_dev, M, (want0 ? 1 : 0) | (want1 ? 2 : 0));
+  p.sdf0 = sdf_hand_dev; p.sdf1 = sdf_obj_dev;
   GradParams g;
   g.grad0 = grad_hand_dev; g.grad1 = grad_obj_dev;
   k1g_launch(p, g, k1g_grid(M, d->num_cus), st);
@@ -990,10 +1060,16 @@ int asdf_decode_points_grad(asdf_decoder_t* d, const float* xyz_dev, int64_t M, 
 }
 
 // the reverse-mode scratch (first use; sized for the largest grid, so no call allocates after it): the workgroups' partial sums
-// [num_cus][kVjpFoldFloats], one d_fold block for callers that pass none, and the loss form's [num_cus][heads] fp64 sums
+// [num_cus][kVjpFoldFloats], one d_fold block for callers that pass none, the loss form's [num_cus][heads] fp64 sums and, each on a
+// 256-byte boundary behind them, asdf_fit_code's sample descriptor and workgroup map [num_cus]
+static_assert(sizeof(FitSampleDesc) <= 256, "the workgroup map lies 256 bytes behind the descriptor");
+static size_t vjp_scratch_desc_at(const asdf_decoder* d) {
+  const size_t sums = ((size_t)d->num_cus + 1) * kVjpFoldFloats * sizeof(float) + (size_t)d->num_cus * kHeads * sizeof(double);
+  return (sums + 255) & ~(size_t)255;
+}
 static int vjp_scratch(asdf_decoder* d) {
   if (d->vjp_partial) return ASDF_OK;
-  const size_t bytes = ((size_t)d->num_cus + 1) * kVjpFoldFloats * sizeof(float) + (size_t)d->num_cus * kHeads * sizeof(double);
+  const size_t bytes = vjp_scratch_desc_at(d) + 256 + (size_t)d->num_cus * sizeof(FitWg);
   const hipError_t e = hipMalloc((void**)&d->vjp_partial, bytes);
   if (e != hipSuccess) { g_last_hip_error = (int)e; d->vjp_partial = nullptr; return e == hipErrorOutOfMemory ? ASDF_ENOMEM : ASDF_EHIP; }
   return ASDF_OK;
@@ -1003,8 +1079,7 @@ int asdf_decode_points_vjp(asdf_decoder_t* d, const float* xyz_dev, int64_t M, c
                            float* sdf_hand_dev, float* sdf_obj_dev, float* d_fold_dev, float* d_latent_dev, float* d_embed_dev, void* stream) {
   if (!d || M < 0 || (M > 0 && !xyz_dev)) return ASDF_EINVAL;
   if (!d->sample_bound) return ASDF_EINVAL;
-  // SeparateDecoder with affine point features and an ordinary (per-sample constant) latent
-  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound || !d->streamT) return ASDF_ENOGRAD;
+  if (!point_list_covered(d) || !d->streamT) return ASDF_ENOGRAD;
   hipStream_t st = (hipStream_t)stream;
   const int heads_mask = (w_hand_dev ? 1 : 0) | (w_obj_dev ? 2 : 0);
   if (M == 0 || !heads_mask) {
@@ -1014,15 +1089,8 @@ int asdf_decode_points_vjp(asdf_decoder_t* d, const float* xyz_dev, int64_t M, c
     return ASDF_OK;
   }
   ASDF_TRY(vjp_scratch(d));
-  // always the fp32 chain's weights and constants: d->math and the MFMA shape of the split-half sweeps are not looked at
-  DecodeParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.stream = d->stream; p.cst = d->cst;
+  DecodeParams p = point_list_params(d, d->cst, xyz_dev, M, heads_mask);
   p.sdf0 = w_hand_dev ? sdf_hand_dev : nullptr; p.sdf1 = w_obj_dev ? sdf_obj_dev : nullptr;
-  p.xyz = xyz_dev; p.P = M; p.N = 1; p.mode = kPointList;
-  p.first_mlp = w_hand_dev ? 0 : 1;
-  p.num_mlps = heads_mask == 3 ? 2 : 1;
-  p.pf = d->spec.point_feats[0];
   VjpParams v;
   v.streamT = d->streamT; v.w[0] = w_hand_dev; v.w[1] = w_obj_dev; v.partial = d->vjp_partial;
   const int grid = k1v_grid(M, d->num_cus);
@@ -1033,60 +1101,39 @@ int asdf_decode_points_vjp(asdf_decoder_t* d, const float* xyz_dev, int64_t M, c
   return ASDF_OK;
 }
 
+// The batch of one on the decoder's own memory: its constants images (the fold is set_sample's, so the sample stays bound to the moving
+// code in every image and the status word counts as ever), its reverse-mode scratch, and the caller's state buffer.
 int asdf_fit_code(asdf_decoder_t* d, const float* xyz_dev, int64_t M, const float* t_hand_dev, int32_t n_hand, const float* t_obj_dev,
                   int32_t n_obj, float clamp, float* z_dev, const float* z0_dev, float prior, const float* step_table_dev, int32_t steps,
                   void* state_dev, size_t state_bytes, double* history_dev, void* stream) {
   if (!d || M < 0 || steps < 0 || n_hand < 0 || n_obj < 0 || (M > 0 && !xyz_dev)) return ASDF_EINVAL;
   if (!d->sample_bound) return ASDF_EINVAL;
-  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound || !d->streamT) return ASDF_ENOGRAD;
+  if (!point_list_covered(d) || !d->streamT) return ASDF_ENOGRAD;
   if (steps == 0 || M == 0) return ASDF_OK;
   if (!z_dev || !step_table_dev || !state_dev || state_bytes < ASDF_FIT_STATE_BYTES || ((uintptr_t)state_dev & 3)) return ASDF_EINVAL;
-  if (!(clamp > 0.0f) || !(prior >= 0.0f) || n_hand > M || n_obj > M) return ASDF_EINVAL;
-  // a head without targets, or with an empty set, is absent
-  const float* t[2] = {n_hand > 0 ? t_hand_dev : nullptr, n_obj > 0 ? t_obj_dev : nullptr};
-  const int heads_mask = (t[0] ? 1 : 0) | (t[1] ? 2 : 0);
+  if (!(clamp > 0.0f) || !(prior >= 0.0f) || n_hand > M || n_obj > M || M > INT32_MAX) return ASDF_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   ASDF_TRY(vjp_scratch(d));
-  float* state = static_cast<float*>(state_dev);
-  float* fold = d->vjp_partial + (size_t)d->num_cus * kVjpFoldFloats;
-  double* loss_partial = reinterpret_cast<double*>(d->vjp_partial + ((size_t)d->num_cus + 1) * kVjpFoldFloats);
-  const double inv_n[2] = {t[0] ? 1.0 / n_hand : 0.0, t[1] ? 1.0 / n_obj : 0.0};
-  DecodeParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.stream = d->stream; p.cst = d->cst;
-  p.xyz = xyz_dev; p.P = M; p.N = 1; p.mode = kPointList;
-  p.first_mlp = t[0] ? 0 : 1;
-  p.num_mlps = heads_mask == 3 ? 2 : 1;
-  p.pf = d->spec.point_feats[0];
-  VjpParams v;
-  v.streamT = d->streamT; v.w[0] = t[0]; v.w[1] = t[1]; v.partial = d->vjp_partial;
-  VjpLossParams q;
-  q.clamp = clamp; q.inv_n[0] = (float)inv_n[0]; q.inv_n[1] = (float)inv_n[1]; q.partial = loss_partial;
-  AdamRule rule;
-  rule.b1 = 0.9f; rule.b2 = 0.999f; rule.eps = 1e-8f; rule.k_prior = (float)(2.0 * (double)prior / kLatent);
-  const int grid = k1v_grid(M, d->num_cus);
-  k1v_adam_init(state, z_dev, z0_dev, st);
-  for (int k = 0; k < steps; ++k) {
-    ASDF_TRY(set_sample_fold(d, z_dev, st));
-    if (heads_mask) {
-      k1v_loss_launch(p, v, q, grid, st);
-      k1v_finish_loss(d->vjp_partial, loss_partial, grid, heads_mask, fold, d->wlat, d->wpt, ASDF_MAX_POINT_FEATS, state + 3 * kLatent,
-                      inv_n[0], inv_n[1], history_dev ? history_dev + k : nullptr, st);
-    } else if (history_dev) {
-      ASDF_HIP(hipMemsetAsync(history_dev + k, 0, sizeof(double), st));      // (no data term: only the prior moves the code)
-    }
-    k1v_adam_step(state, step_table_dev + 2 * (size_t)k, rule, z_dev, st);
-  }
-  ASDF_TRY(set_sample_fold(d, z_dev, st));
-  ASDF_HIP(hipGetLastError());
-  return ASDF_OK;
+  const FitSampleDesc desc = fit_describe(d, 0, M, 0, t_hand_dev ? n_hand : 0, t_obj_dev ? n_obj : 0);
+  char* tail = reinterpret_cast<char*>(d->vjp_partial) + vjp_scratch_desc_at(d);
+  FitBuffers b;
+  b.samples = reinterpret_cast<FitSampleDesc*>(tail);
+  b.wgs = reinterpret_cast<FitWg*>(tail + 256);
+  b.cst = d->cst;
+  b.partial = d->vjp_partial;
+  b.fold = d->vjp_partial + (size_t)d->num_cus * kVjpFoldFloats;
+  b.loss_partial = reinterpret_cast<double*>(d->vjp_partial + ((size_t)d->num_cus + 1) * kVjpFoldFloats);
+  b.state = static_cast<float*>(state_dev);
+  b.xyz = xyz_dev; b.t[0] = t_hand_dev; b.t[1] = t_obj_dev;
+  b.z = z_dev; b.z0 = z0_dev; b.step_table = step_table_dev; b.history = history_dev;
+  ASDF_TRY(fit_loop(d, &desc, 1, b, clamp, prior, steps, st, [&] { return set_sample_fold(d, z_dev, st); }));
+  return set_sample_fold(d, z_dev, st);
 }
 
 // asdf_fit_codes' workspace, every part 256-byte aligned: [descriptors | workgroup map | constants blocks | partial sums | d_fold |
 // loss partials | Adam states].  ASDF_EINVAL where the batch cannot be described (the descriptors' words are 32-bit).
 struct FitCodesLayout {
   size_t samples, wgs, cst, partial, fold, loss, state, bytes;
-  int total_wgs;
 };
 static int fit_codes_layout(const asdf_decoder* d, int32_t B, const int64_t* m, FitCodesLayout* L) {
   if (!d || !m || !L || B < 1 || B > 65535) return ASDF_EINVAL;
@@ -1107,7 +1154,6 @@ static int fit_codes_layout(const asdf_decoder* d, int32_t B, const int64_t* m, 
   L->loss = part((size_t)wgs * kHeads * sizeof(double));
   L->state = part((size_t)B * kFitStateFloats * sizeof(float));
   L->bytes = at;
-  L->total_wgs = (int)wgs;
   return ASDF_OK;
 }
 
@@ -1124,50 +1170,35 @@ int asdf_fit_codes(asdf_decoder_t* d, int32_t B, const float* xyz_dev, const int
                    float prior, const float* step_table_dev, int32_t steps, void* workspace_dev, size_t workspace_bytes,
                    double* history_dev, void* stream) {
   if (!d || B < 1 || steps < 0 || !m || !xyz_dev) return ASDF_EINVAL;
-  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound || !d->streamT) return ASDF_ENOGRAD;
+  if (!point_list_covered(d) || !d->streamT) return ASDF_ENOGRAD;
   if (steps == 0) return ASDF_OK;
   if (!z_dev || !embed_dev || !step_table_dev || !workspace_dev || ((uintptr_t)workspace_dev & 15)) return ASDF_EINVAL;
   if (!(clamp > 0.0f) || !(prior >= 0.0f) || (t_hand_dev && !n_hand) || (t_obj_dev && !n_obj)) return ASDF_EINVAL;
   FitCodesLayout L;
   ASDF_TRY(fit_codes_layout(d, B, m, &L));
   if (workspace_bytes < L.bytes) return ASDF_EINVAL;
-  // the descriptors: a head without targets, or with an empty set, is absent from its sample
   std::vector<FitSampleDesc> descs((size_t)B);
   int first = 0, wg0 = 0;
   for (int s = 0; s < B; ++s) {
     const int64_t nh = t_hand_dev ? n_hand[s] : 0, no = t_obj_dev ? n_obj[s] : 0;
     if (nh < 0 || no < 0 || nh > m[s] || no > m[s] || (nh == 0 && no == 0)) return ASDF_EINVAL;
-    FitSampleDesc& sd = descs[(size_t)s];
-    std::memset(&sd, 0, sizeof(sd));
-    sd.first = first; sd.m = (int)m[s]; sd.grid = k1v_grid(m[s], d->num_cus); sd.wg0 = wg0;
-    sd.heads_mask = (nh > 0 ? 1 : 0) | (no > 0 ? 2 : 0);
-    sd.inv_n_d[0] = nh > 0 ? 1.0 / (double)nh : 0.0; sd.inv_n_d[1] = no > 0 ? 1.0 / (double)no : 0.0;
-    sd.inv_n[0] = (float)sd.inv_n_d[0]; sd.inv_n[1] = (float)sd.inv_n_d[1];
-    first += sd.m; wg0 += sd.grid;
+    descs[(size_t)s] = fit_describe(d, first, m[s], wg0, nh, no);
+    first += descs[(size_t)s].m; wg0 += descs[(size_t)s].grid;
   }
   hipStream_t st = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace_dev);
-  FitSampleDesc* samples = reinterpret_cast<FitSampleDesc*>(ws + L.samples);
-  FitWg* wgs = reinterpret_cast<FitWg*>(ws + L.wgs);
   float* cst_all = reinterpret_cast<float*>(ws + L.cst);
-  float* partial = reinterpret_cast<float*>(ws + L.partial);
-  float* fold = reinterpret_cast<float*>(ws + L.fold);
-  double* loss_partial = reinterpret_cast<double*>(ws + L.loss);
-  float* state = reinterpret_cast<float*>(ws + L.state);
-  // the fp32 chain's weights; the constants come from the workspace, so neither the bound sample nor any image of the decoder is touched
-  DecodeParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.stream = d->stream; p.cst = cst_all;
-  p.xyz = xyz_dev; p.P = 0; p.N = 1; p.mode = kPointList;
-  p.pf = d->spec.point_feats[0];
-  VjpParams v;
-  v.streamT = d->streamT; v.w[0] = t_hand_dev; v.w[1] = t_obj_dev; v.partial = partial;
-  VjpLossParams q;
-  q.clamp = clamp; q.inv_n[0] = q.inv_n[1] = 0.0f; q.partial = loss_partial;
-  VjpBatchParams b;
-  b.samples = samples; b.wgs = wgs; b.cst = cst_all;
-  AdamRule rule;
-  rule.b1 = 0.9f; rule.b2 = 0.999f; rule.eps = 1e-8f; rule.k_prior = (float)(2.0 * (double)prior / kLatent);
+  // the constants come from the workspace, so neither the bound sample nor any image of the decoder is touched
+  FitBuffers b;
+  b.samples = reinterpret_cast<FitSampleDesc*>(ws + L.samples);
+  b.wgs = reinterpret_cast<FitWg*>(ws + L.wgs);
+  b.cst = cst_all;
+  b.partial = reinterpret_cast<float*>(ws + L.partial);
+  b.fold = reinterpret_cast<float*>(ws + L.fold);
+  b.loss_partial = reinterpret_cast<double*>(ws + L.loss);
+  b.state = reinterpret_cast<float*>(ws + L.state);
+  b.xyz = xyz_dev; b.t[0] = t_hand_dev; b.t[1] = t_obj_dev;
+  b.z = z_dev; b.z0 = z0_dev; b.step_table = step_table_dev; b.history = history_dev;
   FoldParams fp;
   std::memset(&fp, 0, sizeof(fp));
   fp.wlat = d->wlat; fp.wpt = d->wpt; fp.bias02 = d->bias02; fp.kp = d->kp;
@@ -1175,18 +1206,8 @@ int asdf_fit_codes(asdf_decoder_t* d, int32_t B, const float* xyz_dev, const int
     fp.pf[h] = d->spec.point_feats[h];
     for (int i = 0; i < 3; ++i) { fp.s2[i][h] = 1.0f; fp.s0[i][h] = 1.0f; }
   }
-  k1vb_describe(descs.data(), B, samples, wgs, st);
   k1vb_cst_init(d->cst, cst_all, B, st);
-  k1vb_adam_init(state, z_dev, z0_dev, B, st);
-  for (int k = 0; k < steps; ++k) {
-    k1vb_fold(fp, z_dev, embed_dev, cst_all, B, st);
-    k1vb_loss_launch(p, v, q, b, L.total_wgs, st);
-    k1vb_finish_loss(samples, B, partial, loss_partial, fold, d->wlat, d->wpt, ASDF_MAX_POINT_FEATS, state,
-                     history_dev ? history_dev + k : nullptr, steps, st);
-    k1vb_adam_step(state, step_table_dev + 2 * (size_t)k, rule, z_dev, B, st);
-  }
-  ASDF_HIP(hipGetLastError());
-  return ASDF_OK;
+  return fit_loop(d, descs.data(), B, b, clamp, prior, steps, st, [&] { k1vb_fold(fp, z_dev, embed_dev, cst_all, B, st); return ASDF_OK; });
 }
 
 int asdf_trace_rays(asdf_decoder_t* d, const float* rays_dev, int64_t M, const asdf_trace_params_t* params,
@@ -1197,19 +1218,11 @@ int asdf_trace_rays(asdf_decoder_t* d, const float* rays_dev, int64_t M, const a
   if (params->max_steps < 1 || params->refine_steps < 0 || !(params->min_step > 0.0f) || !(params->max_step > 0.0f)) return ASDF_EINVAL;
   // (the kernel moves a ray and a bracket as one 16-byte word each)
   if (((uintptr_t)rays_dev | (uintptr_t)bracket_hand_dev | (uintptr_t)bracket_obj_dev) & 15) return ASDF_EINVAL;
-  // SeparateDecoder with affine point features and an ordinary (per-sample constant) latent
-  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound) return ASDF_ENOTRACE;
+  if (!point_list_covered(d)) return ASDF_ENOTRACE;
   const bool want0 = t_hand_dev || status_hand_dev, want1 = t_obj_dev || status_obj_dev;
   if (M == 0 || (!want0 && !want1)) return ASDF_OK;
   hipStream_t st = (hipStream_t)stream;
-  // always the fp32 chain's weights and constants: d->math and the MFMA shape of the split-half sweeps are not looked at
-  DecodeParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.stream = d->stream; p.cst = d->cst;
-  p.P = M; p.N = 1; p.mode = kPointList;
-  p.first_mlp = want0 ? 0 : 1;
-  p.num_mlps = want0 && want1 ? 2 : 1;
-  p.pf = d->spec.point_feats[0];
+  const DecodeParams p = point_list_params(d, d->cst, nullptr, M, (want0 ? 1 : 0) | (want1 ? 2 : 0));
   TraceParams q;
   std::memset(&q, 0, sizeof(q));
   q.rays = rays_dev; q.M = M;
@@ -1229,20 +1242,12 @@ int asdf_project_points(asdf_decoder_t* d, const float* xyz_dev, int64_t M, int3
   if (!d || M < 0 || (M > 0 && !xyz_dev) || !params) return ASDF_EINVAL;
   if (!d->sample_bound) return ASDF_EINVAL;
   if (params->max_iters < 0 || !(params->tol >= 0.0f) || !(params->max_move > 0.0f) || !(params->min_grad2 > 0.0f)) return ASDF_EINVAL;
-  // SeparateDecoder with affine point features and an ordinary (per-sample constant) latent
-  if (d->spec.num_heads != 2 || d->spec.feature_mode != ASDF_FEATURES_AFFINE || d->kp != 2 || d->pixel_bound) return ASDF_ENOPROJECT;
+  if (!point_list_covered(d)) return ASDF_ENOPROJECT;
   if (head < 0 || head >= d->spec.num_heads) return ASDF_EINVAL;
   if (M == 0) return ASDF_OK;
   if (!xyz_out_dev && !sdf_dev && !grad_dev && !sdf_in_dev && !status_dev && !evals_dev) return ASDF_OK;
   hipStream_t st = (hipStream_t)stream;
-  // always the fp32 chain's weights and constants: d->math and the MFMA shape of the split-half sweeps are not looked at
-  DecodeParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.stream = d->stream; p.cst = d->cst;
-  p.xyz = xyz_dev; p.P = M; p.N = 1; p.mode = kPointList;
-  p.first_mlp = head;
-  p.num_mlps = 1;
-  p.pf = d->spec.point_feats[0];
+  const DecodeParams p = point_list_params(d, d->cst, xyz_dev, M, 1 << head);
   ProjectParams q;
   std::memset(&q, 0, sizeof(q));
   q.rule = ProjectRule{params->max_iters, params->tol, params->max_move, params->min_grad2};

@@ -62,36 +62,30 @@ void k1v_launch(const DecodeParams& p, const VjpParams& v, int grid, hipStream_t
 // d_fold -> d_latent [256] / d_embed [heads][max_pf][4] (each may be null)
 void k1v_finish(const float* partial, int grid, int heads_mask, float* d_fold, const float* wlat, const float* wpt, int max_pf,
                 float* d_latent, float* d_embed, hipStream_t st);
-// The LOSS form of the same kernel (asdf_fit_code): VjpParams::w holds per-point targets (NaN: the point is not in that head's set), the
-// weight is made in the kernel - the clamped-L1 term of fit.fit_sample, sdf_mlp_vjp_kernel.h - and the workgroups' fp64 sums of the
-// term go to `partial`.  k1v_finish_loss is k1v_finish for d_latent plus, when `history` is given,
-// *history = sum over the evaluated heads of (the partials in workgroup order) inv_n_d[head].
-struct VjpLossParams {
-  float clamp;          // +inf: unclamped
-  float inv_n[2];       // 1 / (points of the head's set), rounded once from double
-  double* partial;      // [grid][heads]
-};
-void k1v_loss_launch(const DecodeParams& p, const VjpParams& v, const VjpLossParams& q, int grid, hipStream_t st);
-void k1v_finish_loss(const float* partial, const double* loss_partial, int grid, int heads_mask, float* d_fold, const float* wlat,
-                     const float* wpt, int max_pf, float* d_latent, double inv_n_hand, double inv_n_obj, double* history, hipStream_t st);
-// One Adam step of asdf_fit_code on the latent code (one workgroup, a lane per entry), every operation one correctly rounded fp32
-// operation in the order of fit.adam_step_host:
-//   g = d_latent + k_prior (z - z0);  m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  z = z - a (m / (sqrt(v) s + eps))
-// state = [z | m | v | d_latent | z0][kLatent]; step = (a, s) of this step; z is also written to z_out (the next fold reads it).
-constexpr int kFitStateFloats = 5 * kLatent;
-struct AdamRule { float b1, b2, eps, k_prior; };
-void k1v_adam_init(float* state, const float* z, const float* z0, hipStream_t st);      // z, z0 (null: z) in; m = v = 0
-void k1v_adam_step(float* state, const float* step, AdamRule rule, float* z_out, hipStream_t st);
-// The same stream of launches over a BATCH of samples (asdf_fit_codes, k1vb_kernels.hip): every sample has its own point list, targets,
-// code, embedding, constants block, partial sums and Adam state, and inside a sample everything is as above - sample s runs
+// THE FIT (asdf_fit_codes over B >= 1 samples, asdf_fit_code its B = 1; k1vb_kernels.hip): per step a fold, the LOSS form of the
+// kernel above, its finish and an Adam step, every launch carrying all B samples.  In the loss form VjpParams::w holds per-point
+// targets (NaN: the point is not in that head's set), the weight is made in the kernel - the clamped-L1 term of fit.fit_sample,
+// sdf_mlp_vjp_kernel.h - and the workgroups' fp64 sums of the term go to VjpLossParams::partial.
+// Every sample has its own point list, targets, code, embedding, constants block, partial sums and Adam state - sample s runs
 // grid_s = k1v_grid(m_s, num_cus) workgroups, workgroup g of it takes tiles g, g + grid_s, ... of its list, and every sum keeps its
 // order - so a sample's bits do not depend on its company.  The launch of the loss form has sum_s grid_s workgroups.
+struct VjpLossParams {
+  float clamp;          // +inf: unclamped
+  float inv_n[2];       // 1 / (points of the head's set), rounded once from double: the kernel takes them from its sample's descriptor
+  double* partial;      // [sum of grids][heads]
+};
+// The Adam step on a latent code (one workgroup per sample, a lane per entry), every operation one correctly rounded fp32 operation in
+// the order of fit.adam_step_host:
+//   g = d_latent + k_prior (z - z0);  m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  z = z - a (m / (sqrt(v) s + eps))
+// a sample's state = [z | m | v | d_latent | z0][kLatent]; step = (a, s) of this step; z is also written to z_out (the next fold reads it).
+constexpr int kFitStateFloats = 5 * kLatent;
+struct AdamRule { float b1, b2, eps, k_prior; };
 struct FitSampleDesc {     // device-resident, read-only to the step's kernels
   int first;               // the sample's first point in the concatenated lists
   int m;                   // its points
-  int grid;                // its workgroups: k1v_grid(m, num_cus)
+  int grid;                // its workgroups: k1v_grid(m, num_cus); 0 with heads_mask == 0
   int wg0;                 // its first workgroup in the launch = its first row of the partial sums
-  int heads_mask;          // bit h: head h has targets in this sample
+  int heads_mask;          // bit h: head h has targets in this sample (0: no data term - d_latent and the history come out as zeros)
   float inv_n[2];          // 1 / (points of the head's set), rounded once from double
   int pad;
   double inv_n_d[2];       // ... and in double, for the history

@@ -1,8 +1,7 @@
-// K1VB: asdf_fit_codes' stream of launches - the fit of k1v_kernels.hip over a batch of samples.  The loss form of the reverse-mode
-// body (sdf_mlp_vjp_kernel.h) in its BATCH instantiation, where a workgroup first looks up its sample, and per-sample forms of the small
-// kernels around it (fold, reduce, adjoint, loss reduce, Adam), each a grid dimension over the samples around the one-sample body.
+// K1VB: the fit's stream of launches over B >= 1 samples (asdf_fit_codes; asdf_fit_code is B = 1).  The LOSS form of the reverse-mode
+// body (sdf_mlp_vjp_kernel.h), where a workgroup first looks up its sample, and per-sample forms of the small kernels around it (fold,
+// reduce, adjoint, loss reduce, Adam), each a grid dimension over the samples around the one-sample body.
 // A unit of its own, built with k1v_kernels.hip's flags, so that every other unit compiles to the same code as without it.
-#define ASDF_VJP_BODIES_ONLY
 #include "k1_launch.h"
 #include "fold_body.h"
 #include "sdf_mlp_vjp_kernel.h"
@@ -79,7 +78,7 @@ __global__ __launch_bounds__(256) void vjp_adjoint_batch_kernel(const float* __r
   vjp_adjoint_body(d_fold + s * kVjpFoldFloats, wlat, wpt, max_pf, state + s * kFitStateFloats + 3 * kLatent, nullptr, blockIdx.x);
 }
 
-// vjp_loss_reduce_kernel, sample blockIdx.x: history[s][k]
+// the data term of one step (vjp_loss_total), sample blockIdx.x: history[s][k]
 __global__ void vjp_loss_reduce_batch_kernel(const FitSampleDesc* __restrict__ samples, const double* __restrict__ loss_partial,
                                              double* __restrict__ history, long long history_stride) {
   if (threadIdx.x != 0) return;

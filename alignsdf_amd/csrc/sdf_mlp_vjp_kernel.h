@@ -169,22 +169,22 @@ __device__ __forceinline__ double half_sum_f64(double v) {
 
 // p.mode == kPointList, affine point features (KP == 2), SeparateDecoder; p.sdf0 / p.sdf1 may be null.  The host evaluates a head only
 // when its weights v.w[head] are given.
-// LOSS (the fit form, asdf_fit_code): v.w[head] holds per-point TARGETS t instead of weights, and the weight is formed where the value
-// f is: with c = q.clamp,  r = clip(f, -c, c) - clip(t, -c, c),  l = |r|,  w = (t is NaN or f < -c or f > c) ? 0 : sign(r) q.inv_n[head]
+// LOSS (the fit form, k1vb_kernels.hip): v.w[head] holds per-point TARGETS t instead of weights, and the weight is formed where the
+// value f is: with c = q.clamp,  r = clip(f, -c, c) - clip(t, -c, c),  l = |r|,  w = (t is NaN or f < -c or f > c) ? 0 : sign(r) q.inv_n[head]
 // - the clamped-L1 term of fit.fit_sample and its autograd weight (sign(0) = 0, the clamp's mask inclusive as torch.clamp's backward).
 // A NaN target takes the point out of the head's set (l = 0, w = 0).  The l of a workgroup's points are added in fp64 (per tile: the
 // half's butterfly, then the wave's LDS word; the waves in wave order) into q.partial[workgroup][head].  Everything behind w is the
 // reverse phase of the weight form, the same text.
-// BATCH (asdf_fit_codes, k1vb_kernels.hip): the launch carries several point lists.  The body depends on its launch only through the
-// workgroup's index and the launch's size, p.P / xyz / cst / first_mlp / num_mlps, v.w[] / partial and q.inv_n[] / partial;
-// sdf_mlp_vjp_batch_body below makes those for the workgroup's sample and hands in its index inside the sample (wg) and the sample's
-// own grid (nwg) - everything behind this line is then the one-list form, the same text.
-template <bool LOSS, bool BATCH = false>
-__device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const VjpParams& v, const VjpLossParams& q, unsigned batch_wg = 0,
-                                                 unsigned batch_nwg = 0) {
-  // (read where they are used, as the one-list form always has: made once up here, the launch's size lives across the tile loop)
-  auto wg = [&]() -> unsigned { if constexpr (BATCH) return batch_wg; else return blockIdx.x; };
-  auto nwg = [&]() -> unsigned { if constexpr (BATCH) return batch_nwg; else return gridDim.x; };
+// Its launch carries the point lists of B >= 1 samples.  The body depends on its launch only through the workgroup's index and the
+// launch's size, p.P / xyz / cst / first_mlp / num_mlps, v.w[] / partial and q.inv_n[] / partial; sdf_mlp_vjp_batch_body below makes
+// those for the workgroup's sample and hands in its index inside the sample (sample_wg) and the sample's own grid (sample_nwg) -
+// everything behind this line is then the one-list form, the same text.
+template <bool LOSS>
+__device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const VjpParams& v, const VjpLossParams& q, unsigned sample_wg = 0,
+                                                 unsigned sample_nwg = 0) {
+  // (read where they are used, as the weight form always has: made once up here, the launch's size lives across the tile loop)
+  auto wg = [&]() -> unsigned { if constexpr (LOSS) return sample_wg; else return blockIdx.x; };
+  auto nwg = [&]() -> unsigned { if constexpr (LOSS) return sample_nwg; else return gridDim.x; };
   constexpr int KP = 2;
   using CL = CstLayout<KP>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -210,7 +210,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
     const int head = p.first_mlp + slot;
     const float* hc = cst;
     const float* wgt;
-    if constexpr (BATCH) wgt = head ? v.w[1] : v.w[0];      // (v and q are the workgroup's own copies there: no indexed reads of them)
+    if constexpr (LOSS) wgt = head ? v.w[1] : v.w[0];      // (v and q are the workgroup's own copies there: no indexed reads of them)
     else wgt = v.w[head];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -250,7 +250,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
       // the bases are made opaque per tile so that the per-lane source addresses are not hoisted out of the tile loop (spills)
       const float* fbase = fwd0;
       const float* rbase = rev0;
-      if constexpr (BATCH) {      // (derived from descriptor words: named uniform where the constraint below needs a scalar)
+      if constexpr (LOSS) {      // (derived from descriptor words: named uniform where the constraint below needs a scalar)
         fbase = uniform_ptr(fbase);
         rbase = uniform_ptr(rbase);
       }
@@ -375,7 +375,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
           const float c = q.clamp;
           const bool in_set = t == t;
           const float r = __fsub_rn(fminf(fmaxf(sdf, -c), c), fminf(fmaxf(t, -c), c));
-          auto inv_n = [&]() -> float { if constexpr (BATCH) return head ? q.inv_n[1] : q.inv_n[0]; else return q.inv_n[head]; };
+          auto inv_n = [&]() -> float { return head ? q.inv_n[1] : q.inv_n[0]; };      // (selected at each use)
           const float sgn = r > 0.0f ? inv_n() : (r < 0.0f ? -inv_n() : 0.0f);
           const double l = half_sum_f64(in_set && half == 0 ? (double)fabsf(r) : 0.0);
           if (lane == 0) lsum[wave] += l;
@@ -514,7 +514,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_body(const DecodeParams& p, const Vj
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// The batched loss form (asdf_fit_codes): workgroup blockIdx.x of the launch is workgroup b.wgs[blockIdx.x].g of sample
+// The loss form's kernel body: workgroup blockIdx.x of the launch is workgroup b.wgs[blockIdx.x].g of sample
 // b.wgs[blockIdx.x].sample.  The two words and the sample's descriptor are read with uniform addresses and held in scalar registers
 // (nothing is written through them: descriptors are read-only to this kernel); p.xyz, v.w[] are the concatenated lists of the batch,
 // v.partial / q.partial the rows of the whole launch, and the sample's share of each starts at its first point / first workgroup.
@@ -539,7 +539,7 @@ __device__ __forceinline__ void sdf_mlp_vjp_batch_body(const DecodeParams& p, co
   qs.inv_n[0] = __int_as_float(uniform_i(__float_as_int(sd->inv_n[0])));
   qs.inv_n[1] = __int_as_float(uniform_i(__float_as_int(sd->inv_n[1])));
   qs.partial = q.partial + (size_t)wg0 * kHeads;
-  sdf_mlp_vjp_body<true, true>(ps, vs, qs, (unsigned)g, (unsigned)grid);
+  sdf_mlp_vjp_body<true>(ps, vs, qs, (unsigned)g, (unsigned)grid);
 }
 
 // d_fold [2 heads][2 layers][512][4] = the workgroups' partials added in workgroup order (fp64 accumulator); a head that was not
@@ -640,20 +640,5 @@ __device__ __forceinline__ void adam_step_body(float* __restrict__ state, const 
   state[2 * kLatent + i] = v;
   z_out[i] = z;
 }
-
-// (the one-list kernels of these bodies; k1vb_kernels.hip, which has its own per-sample forms, leaves them out)
-#ifndef ASDF_VJP_BODIES_ONLY
-__global__ __launch_bounds__(256) void vjp_reduce_kernel(const float* __restrict__ partial, int grid, int heads_mask, float* __restrict__ d_fold) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= kVjpFoldFloats) return;
-  vjp_reduce_entry(partial, grid, heads_mask, d_fold, e);
-}
-
-__global__ __launch_bounds__(256) void vjp_adjoint_kernel(const float* __restrict__ d_fold, const float* __restrict__ wlat,
-                                                          const float* __restrict__ wpt, int max_pf, float* __restrict__ d_latent,
-                                                          float* __restrict__ d_embed) {
-  vjp_adjoint_body(d_fold, wlat, wpt, max_pf, d_latent, d_embed, blockIdx.x);
-}
-#endif
 
 }  // namespace asdf

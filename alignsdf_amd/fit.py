@@ -171,8 +171,9 @@ def fit_sample(decoder, latent, embed, surface_hand=None, surface_obj=None, step
 
 
 # ---- auto-decode: the code alone, against SDF targets, on the device ----------------------------------------------------------------------
-# One rule, stated three times: asdf_fit_code (csrc/decoder.hip: every step a stream of launches), fit_code_lockstep below (one step at a
-# time, the weights made in torch, the step on the host) and - operation by operation - clamped_l1_rule and adam_step_host.
+# One rule, one device loop: fit_loop of csrc/decoder.hip (every step a stream of launches over B >= 1 samples) behind both asdf_fit_codes
+# and asdf_fit_code, its batch of one.  Beside it the rule stands twice on the host: fit_code_lockstep below (one step at a time, the
+# weights made in torch, the step on the host) and - operation by operation - clamped_l1_rule and adam_step_host.
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8
 
 
@@ -197,8 +198,8 @@ def prior_factor(prior, latent_size, dtype=np.float32):
 
 def adam_step_host(z, m, v, d_latent, z0, k_prior, a, s, b1=ADAM_B1, b2=ADAM_B2, eps=ADAM_EPS):
     """THE DEFINITION of the fit's Adam step, in numpy, in the dtype of z (fp32 in the product; fp64 as the tests' yardstick) - every
-    line below is one correctly rounded operation per element, in this order, and the device step (csrc/k1v_kernels.hip:
-    adam_step_kernel) equals it in every bit:
+    line below is one correctly rounded operation per element, in this order, and the device step (csrc/k1vb_kernels.hip:
+    adam_step_batch_kernel) equals it in every bit:
         g = d_latent + k_prior (z - z0)
         m = b1 m + (1 - b1) g
         v = b2 v + ((1 - b2) g) g

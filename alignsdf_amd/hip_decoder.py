@@ -1409,10 +1409,10 @@ class HipSdfDecoder:
 
     def fit_code(self, xyz, t_hand, t_obj, n_hand, n_obj, latent, z0=None, steps=800, lr=5e-3, decay=0.1, every=400, prior=1e-4,
                  clamp=0.05):
-        """Auto-decode on the device (asdf_fit_code): `steps` Adam steps on the latent code against per-point SDF targets, enqueued
-        as one stream of launches - fold, the loss form of the reverse-mode kernel, its finish, the Adam step - with nothing read
-        back and no wait.  xyz [M, 3]; t_hand / t_obj [M] targets of each head (None: the head is left out), NaN where a point is
-        not in that head's set; n_hand / n_obj the number of non-NaN targets (the caller's count - the targets are not read back to
+        """Auto-decode on the device (asdf_fit_code: fit_codes' device loop over a batch of one, on the bound sample): `steps` Adam
+        steps on the latent code against per-point SDF targets, enqueued as one stream of launches - fold, the loss form of the
+        reverse-mode kernel, its finish, the Adam step - with nothing read back and no wait.  xyz [M, 3]; t_hand / t_obj [M]
+        targets of each head (None: the head is left out), NaN where a point is not in that head's set; n_hand / n_obj the number of non-NaN targets (the caller's count - the targets are not read back to
         count them).  The loss is fit.fit_sample's clamped-L1 term per head plus prior mean((z - z0)^2) (z0 None: the start code);
         the rate of step k is lr decay^(k // every) (fit.adam_step_table).  The point embedding is the one set_sample bound; only
         the code moves.  Returns (latent [L], history [steps] fp64: the data term before each step) as device tensors; the decoder
@@ -1424,18 +1424,9 @@ class HipSdfDecoder:
             raise NotImplementedError("the fit kernel does not cover this decoder: %s" % why)
         if self._bound is None:
             raise ValueError("fit_code: bind the sample (its point embedding) with set_sample first")
-        dev32 = lambda t: t.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        xyz = dev32(xyz)
+        dev32 = self._dev32
+        xyz, ts = self._fit_lists(xyz, (("t_hand", t_hand), ("t_obj", t_obj)))
         M, steps = xyz.shape[0], int(steps)
-        if xyz.dim() != 2 or xyz.shape[1] != 3:
-            raise ValueError("xyz has shape %s, expected [M, 3]" % (tuple(xyz.shape),))
-        ts = []
-        for name, t in (("t_hand", t_hand), ("t_obj", t_obj)):
-            if t is not None:
-                t = dev32(t).reshape(-1)
-                if t.numel() != M:
-                    raise ValueError("%s has %d elements, expected %d" % (name, t.numel(), M))
-            ts.append(t)
         z = dev32(latent).reshape(-1).clone()
         if z.numel() != self.latent_size:
             raise ValueError("latent has %d elements, expected %d" % (z.numel(), self.latent_size))
@@ -1458,9 +1449,26 @@ class HipSdfDecoder:
             self._latent = z
         return z, history
 
-    def fit_codes_refusal(self):
-        """Why fit_codes would refuse this decoder, or None: fit_code_refusal()."""
-        return self.fit_code_refusal()
+    fit_codes_refusal = fit_code_refusal      # (fit_codes refuses what fit_code refuses)
+
+    def _dev32(self, t):
+        return torch.as_tensor(t).detach().to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _fit_lists(self, xyz, targets, sample=None):
+        """One sample's lists as fit_code / fit_codes check them: xyz [m, 3] and targets = ((name, [m] or None), ...) -> (xyz, [targets])
+        as contiguous fp32 device tensors.  `sample`: its place in a batch (where m >= 1), for the messages."""
+        batch = sample is not None
+        xyz = self._dev32(xyz)
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or (batch and xyz.shape[0] < 1):
+            raise ValueError("xyz has shape %s, expected %s" % (tuple(xyz.shape), "[m, 3] with m >= 1" if batch else "[M, 3]"))
+        out = []
+        for name, t in targets:
+            if t is not None:
+                t = self._dev32(t).reshape(-1)
+                if t.numel() != xyz.shape[0]:
+                    raise ValueError("%s%s has %d elements, expected %d" % (name, " of sample %d" % sample if batch else "", t.numel(), xyz.shape[0]))
+            out.append(t)
+        return xyz, out
 
     def _fit_table(self, steps, lr, decay, every):
         """fit_code's cache of step tables on the device, per schedule and stream."""
@@ -1489,35 +1497,30 @@ class HipSdfDecoder:
         why = self.fit_codes_refusal()
         if why is not None:
             raise NotImplementedError("the fit kernel does not cover this decoder: %s" % why)
-        dev32 = lambda t: torch.as_tensor(t).detach().to(device=self.device, dtype=torch.float32).contiguous()
+        dev32 = self._dev32
         B, steps = len(xyz_list), int(steps)
         if B < 1:
             raise ValueError("fit_codes: an empty batch")
-        xs = [dev32(x) for x in xyz_list]
-        for x in xs:
-            if x.dim() != 2 or x.shape[1] != 3 or x.shape[0] < 1:
-                raise ValueError("xyz has shape %s, expected [m, 3] with m >= 1" % (tuple(x.shape),))
-        ms = [int(x.shape[0]) for x in xs]
-        ts, ns = [], []
+        heads = []
         for name, tl, nl in (("t_hand", t_hand_list, n_hand), ("t_obj", t_obj_list, n_obj)):
             if tl is None or all(t is None for t in tl):
+                tl = [None] * B
+            elif len(tl) != B or len(nl) != B:
+                raise ValueError("%s: %d lists and %d counts for %d samples" % (name, len(tl), len(nl), B))
+            heads.append((name, tl, nl))
+        lists = [self._fit_lists(x, [(name, tl[s]) for name, tl, _ in heads], sample=s) for s, x in enumerate(xyz_list)]
+        ms = [int(x.shape[0]) for x, _ in lists]
+        ts, ns = [], []
+        for h, (_, _, nl) in enumerate(heads):
+            tl = [t[h] for _, t in lists]
+            if all(t is None for t in tl):
                 ts.append(None)
                 ns.append(None)
                 continue
-            if len(tl) != B or len(nl) != B:
-                raise ValueError("%s: %d lists and %d counts for %d samples" % (name, len(tl), len(nl), B))
-            parts = []
-            for s, t in enumerate(tl):
-                if t is None:
-                    parts.append(torch.full((ms[s],), float("nan"), dtype=torch.float32, device=self.device))
-                else:
-                    t = dev32(t).reshape(-1)
-                    if t.numel() != ms[s]:
-                        raise ValueError("%s of sample %d has %d elements, expected %d" % (name, s, t.numel(), ms[s]))
-                    parts.append(t)
-            ts.append(torch.cat(parts))
+            nan = lambda m: torch.full((m,), float("nan"), dtype=torch.float32, device=self.device)
+            ts.append(torch.cat([nan(m) if t is None else t for m, t in zip(ms, tl)]))
             ns.append((ctypes.c_int32 * B)(*[0 if t is None else int(n) for t, n in zip(tl, nl)]))
-        xyz = torch.cat(xs, 0)
+        xyz = torch.cat([x for x, _ in lists], 0)
         z = dev32(latents).reshape(B, -1).clone()
         if z.shape[1] != self.latent_size:
             raise ValueError("latents have %d elements each, expected %d" % (z.shape[1], self.latent_size))

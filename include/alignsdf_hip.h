@@ -325,7 +325,8 @@ int asdf_decode_points_vjp(asdf_decoder_t* dec, const float* xyz_dev, int64_t M,
  * No persistent kernel, no barrier between workgroups, no graph: separate launches.  Every sum is taken in a fixed order: the same
  * call twice gives the same bits.  steps == 0 or M == 0: ASDF_OK, nothing is launched, z_dev stays.  Not re-entrant per decoder (the
  * scratch of asdf_decode_points_vjp).  ASDF_EINVAL / ASDF_ENOGRAD as asdf_decode_points_vjp; ASDF_EINVAL also for steps < 0, a count
- * < 0 or > M, clamp not > 0, prior < 0 and - with work to do - NULL z_dev / step_table_dev / state_dev or a state buffer too small.
+ * < 0 or > M, clamp not > 0, prior < 0 and - with work to do - NULL z_dev / step_table_dev / state_dev or a state buffer too small,
+ * or M > 2^31 - 1 (the call is asdf_fit_codes' loop over a batch of one, whose sample descriptors are 32-bit).
  * (Looked up by name like asdf_decode_points_vjp: asdf_version() stays 132.) */
 #define ASDF_FIT_STATE_BYTES 5120
 int asdf_fit_code(asdf_decoder_t* dec, const float* xyz_dev, int64_t M, const float* t_hand_dev, int32_t n_hand, const float* t_obj_dev,

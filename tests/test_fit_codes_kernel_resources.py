@@ -1,11 +1,11 @@
-"""Compile-time budget of the batched fit's kernels (csrc/k1vb_kernels.hip), from the compiler's resource remarks only, after the pattern of
-tests/test_fit_code_kernel_resources.py: the batched loss form of the reverse-mode kernel has no scratch, spills no vector register,
+"""Compile-time budget of the fit's kernels (csrc/k1vb_kernels.hip), from the compiler's resource remarks only, after the pattern of
+tests/test_fit_code_kernel_resources.py: the loss form of the reverse-mode kernel has no scratch, spills no vector register,
 fits the 512 registers of one wave per SIMD, and the small per-sample kernels around it have no scratch and no spills at all.
 
-The batched loss form is the one-list body behind a descriptor lookup, so like that body it keeps scalar values in lanes of a vector
+The loss form is the one-list body behind a descriptor lookup, so like that body it keeps scalar values in lanes of a vector
 register (no memory involved - its ScratchSize is 0; tests/test_fit_code_kernel_resources.py explains).  Their number is held at no more than the 58
-it was first built with (the one-list loss form: 53; the descriptor's words - the sample's workgroup index and grid, its point count
-and its pointers - are the difference)."""
+it was first built with (the weight form: 39; the loss term's words and the descriptor's - the sample's workgroup index and grid, its
+point count and its pointers - are the difference)."""
 import os
 import re
 import subprocess

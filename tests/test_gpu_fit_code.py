@@ -1,5 +1,5 @@
 """Auto-decode on the device (asdf_fit_code: csrc/decoder.hip, the loss form of csrc/sdf_mlp_vjp_kernel.h, the Adam step of
-csrc/k1v_kernels.hip; HipSdfDecoder.fit_code; alignsdf_amd.fit.fit_code / fit_code_lockstep; alignsdf_amd.autodecode).
+csrc/k1vb_kernels.hip - the fit's one loop over a batch of one; HipSdfDecoder.fit_code; alignsdf_amd.fit.fit_code / fit_code_lockstep; alignsdf_amd.autodecode).
 
 The device loop is held to the same rule taken one step at a time with the host in the loop - bit for bit in the code, to the rounding
 of an fp64 sum in the history -, its gradient to the fp64 reverse chain of tests/sdf_vjp_cases, its outcome to the rule run in fp64 on
@@ -217,6 +217,38 @@ def test_no_work_leaves_the_code_and_refusals_are_refusals(decoders):
         with pytest.raises(NotImplementedError, match=word):
             dec.fit_code(x, t33, None, 33, 0, latent, steps=1)
         dec.close()
+    assert np.array_equal(_bits(zc), _bits(latent))
+
+
+def test_no_head_has_targets_only_the_prior_moves_the_code(decoders):
+    """n_hand = n_obj = 0 with M > 0: no data term.  The code takes `steps` Adam steps on the prior alone - adam_step_host with d_latent =
+    0, bit for bit -, the history is exactly zero, and the decoder is left bound to the result.  The C call answers ASDF_OK."""
+    from alignsdf_amd.fit import adam_step_host, adam_step_table, prior_factor
+    hip = decoders(TAG)
+    latent, embed = _bind(hip, TAG, SAMPLE)
+    M, steps = 33, 3
+    x = _cuda(vc.list_points(M))
+    z, history = hip.fit_code(x, None, None, 0, 0, latent, z0=torch.zeros(L), steps=steps, lr=LR, decay=0.5, every=2, prior=0.5, clamp=CLAMP)
+    bound = [_np(v).copy() for v in _f32_values(hip, x)]
+    zero = np.zeros(L, np.float32)
+    want, m, v = _np(latent), zero, zero
+    for a, s in adam_step_table(steps, LR, 0.5, 2):
+        want, m, v = adam_step_host(want, m, v, zero, zero, prior_factor(0.5, L), a, s)
+    assert np.array_equal(_bits(z), _bits(want)) and not np.array_equal(_bits(z), _bits(latent))
+    assert tuple(history.shape) == (steps,) and not _np(history).view(np.int64).any(), _np(history)
+    assert not _np(hip._fit_state[3 * L:4 * L]).view(np.int32).any(), "d_latent is +0"
+    hip.set_sample(z.reshape(1, -1), embed)
+    assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(bound, _f32_values(hip, x)))
+    # the ABI, directly: one step without targets
+    _bind(hip, TAG, SAMPLE)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    zc, table = latent.clone().cuda(), _cuda(adam_step_table(1, LR).reshape(-1))
+    state = torch.empty(_native.FIT_STATE_BYTES // 4, device="cuda")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    code = _native.lib().asdf_fit_code(hip._h, ptr(x), M, None, 0, None, 0, ctypes.c_float(CLAMP), ptr(zc), None, ctypes.c_float(0.5), ptr(table), 1,
+                                       ptr(state), _native.FIT_STATE_BYTES, None, st)
+    torch.cuda.synchronize()
+    assert code == 0                                           # ASDF_OK; (z0 = the start code: the prior's gradient is 0 and the code stays)
     assert np.array_equal(_bits(zc), _bits(latent))
 
 

@@ -1,8 +1,10 @@
 """Many samples' codes fitted in one stream of launches (asdf_fit_codes: csrc/decoder.hip, csrc/k1vb_kernels.hip;
 HipSdfDecoder.fit_codes; alignsdf_amd.fit.fit_codes; autodecode --batch).
 
-The oracle is today's one-sample call: HipSdfDecoder.fit_code on a SECOND decoder object bound with set_sample.  Every sample of a batch
-must come out with exactly its bits - the code and the fp64 history - whatever its position and company."""
+The oracle is the one-sample call: HipSdfDecoder.fit_code on a SECOND decoder object bound with set_sample.  Every sample of a batch
+must come out with exactly its bits - the code and the fp64 history - whatever its position and company.  That call runs the same
+device loop over a batch of one (on the decoder's own constants images and scratch), so one test anchors the batch outside the fit's
+kernels: fit.fit_code_lockstep, the rule one step at a time with the host in the loop."""
 import ctypes
 import json
 import os
@@ -90,15 +92,20 @@ def _same_bits(z, h, want, what):
     assert np.array_equal(_np(h).view(np.int64), wh.view(np.int64)), (what, "history", _np(h), wh)
 
 
+def _four(variant):
+    """The B = 4 batch of the first two tests: (items, the target variant of each)."""
+    z0s = (torch.zeros(L), None, torch.from_numpy(syn.latent_code(9)).reshape(-1), None)
+    kinds = [variant] * 4 if variant != "mixed" else ["obj", "both", "disjoint", "hand"]
+    return [_item(s, M, kind, z0) for s, M, kind, z0 in zip(SAMPLES, LENGTHS, kinds, z0s)], kinds
+
+
 # ---- 1. each sample equals fit_code alone ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant", fc.VARIANTS + ("mixed",))
 def test_each_sample_of_a_batch_equals_fit_code_alone(variant, pair):
     """B = 4, M = 1, 127, 129, 300; every target variant, and "mixed": a different variant per sample, so that the heads differ inside
     one launch.  z0 is given for samples 0 and 2 and defaulted for 1 and 3.  ("disjoint" at M = 1 leaves the object's set empty.)"""
     hip, oracle = pair
-    z0s = (torch.zeros(L), None, torch.from_numpy(syn.latent_code(9)).reshape(-1), None)
-    kinds = [variant] * 4 if variant != "mixed" else ["obj", "both", "disjoint", "hand"]
-    items = [_item(s, M, kind, z0) for s, M, kind, z0 in zip(SAMPLES, LENGTHS, kinds, z0s)]
+    items, kinds = _four(variant)
     z, h = _batch(hip, items, RULE)
     assert tuple(z.shape) == (4, L) and tuple(h.shape) == (4, RULE["steps"]) and h.dtype == torch.float64
     for s, (it, kind) in enumerate(zip(items, kinds)):
@@ -109,6 +116,23 @@ def test_each_sample_of_a_batch_equals_fit_code_alone(variant, pair):
     # (a sample whose points all lie beyond the clamp, with its prior centred on its start, rightly stays: not every code moves)
     moved = [not np.array_equal(_bits(z[s]), _bits(it["latent"])) for s, it in enumerate(items)]
     assert sum(moved) >= 2, moved
+
+
+def test_each_sample_of_a_batch_equals_the_lockstep_loop(pair):
+    """The anchor that is not the batch of one: fit.fit_code_lockstep on the oracle's decoder takes the rule one step at a time through
+    decode_points, the weight form of the reverse-mode kernel and adam_step_host on the host - no kernel of the fit.  The "mixed"
+    batch above: every code to the bit, every history to the rounding of an fp64 sum (1e-12 relative, as
+    tests/test_gpu_fit_code.py::test_k_steps_equal_the_lockstep_loop holds the same comparison)."""
+    from alignsdf_amd.fit import fit_code_lockstep
+    hip, oracle = pair
+    items, kinds = _four("mixed")
+    z, h = _batch(hip, items, RULE)
+    for s, (it, kind) in enumerate(zip(items, kinds)):
+        zl, hl = fit_code_lockstep(oracle, it["latent"], it["embed"], it["x"], it["th"], it["to"], it["nh"], it["no"], z0=it["z0"], **RULE)
+        rel = float(((h[s] - hl).abs() / hl.abs()).max())
+        print("FITCODES lockstep sample %d M=%-3d %-8s: history vs lockstep rel %.1e" % (s, LENGTHS[s], kind, rel))
+        assert np.array_equal(_bits(z[s]), _bits(zl)), (s, kind, float((z[s] - zl).abs().max()))
+        assert ((h[s] - hl).abs() <= 1e-12 * hl.abs()).all(), (s, kind, rel)
 
 
 # ---- 2. more workgroups than compute units, and the persistent stride ----------------------------------------------------------------------------

@@ -3,9 +3,11 @@
 per-sample time of the autodecode flow.
 
   1. M in {1024, 16384} targets (half per head, both heads: the decoder's own fields at another code), STEPS steps, wall time per
-     step after a warm-up call, the two loops interleaved, median of REPS rounds.  fit_code's time includes the one wait at its end.
+     step after a warm-up call, the two loops interleaved, median of REPS rounds and fit_code's fastest and slowest round.  fit_code's
+     time includes the one wait at its end.
   2. autodecode.DeviceFitter on two grasp scenes (meshes by marching cubes of the grasp3 decoder's own fields at N = 64), the
-     flow's defaults (800 steps, 12000 + 4000 samples per head): wall time per sample, mesh loading and sampling included.
+     flow's defaults (800 steps, 12000 + 4000 samples per head): wall time per sample, mesh loading and sampling included, median
+     and range of FLOW_REPS runs.
 
     python tools/time_fit_code.py [--label "<commit>"] > profiles/fit_code.txt"""
 import argparse
@@ -23,6 +25,7 @@ from alignsdf_amd.networks.model import build_decoder  # noqa: E402
 
 REPS = int(os.environ.get("ASDF_TIMING_REPS", "5"))
 STEPS = int(os.environ.get("ASDF_TIMING_STEPS", "100"))
+FLOW_REPS = int(os.environ.get("ASDF_TIMING_FLOW_REPS", "3"))
 
 
 def wall(fn):
@@ -76,8 +79,9 @@ def main():
             for k, fn in loops.items():
                 times[k].append(wall(fn) / STEPS)
         med = {k: float(np.median(v)) for k, v in times.items()}
-        print("M=%-6d fit_sample %.3f ms / step | fit_code %.3f ms / step | fit_sample / fit_code %.2f x | data term fit_sample %.3e -> %.3e, "
-              "fit_code %.3e -> %.3e" % (M, med["fit_sample"], med["fit_code"], med["fit_sample"] / med["fit_code"], *ends["fit_sample"], *ends["fit_code"]))
+        print("M=%-6d fit_sample %.3f ms / step | fit_code %.4f ms / step (rounds %.4f .. %.4f) | fit_sample / fit_code %.2f x | data term "
+              "fit_sample %.3e -> %.3e, fit_code %.3e -> %.3e" % (M, med["fit_sample"], med["fit_code"], min(times["fit_code"]), max(times["fit_code"]),
+                                                                   med["fit_sample"] / med["fit_code"], *ends["fit_sample"], *ends["fit_code"]))
     hip.close()
 
     tag, N = "grasp3", 64
@@ -103,11 +107,14 @@ def main():
         hip.close()
         fitter = ad.DeviceFitter(module, specs)
         ad.run(specs, fitter, "obman", root, os.path.join(root, "warm"), end=1)
-        t0 = time.perf_counter()
-        _, records = ad.run(specs, fitter, "obman", root, os.path.join(root, "codes"))
-        per = 1e3 * (time.perf_counter() - t0) / len(records)
-        print("autodecode flow: %d grasp3 scenes, %d steps, %d + %d samples per head: %.1f ms per sample (wall, meshes read and sampled, code written); %s" % (
-            len(records), records[0]["steps"], ad.SAMPLE_DEFAULTS["near"], ad.SAMPLE_DEFAULTS["uniform"], per, ad.summary_line(records)))
+        per = []
+        for _ in range(FLOW_REPS):
+            t0 = time.perf_counter()
+            _, records = ad.run(specs, fitter, "obman", root, os.path.join(root, "codes"))
+            per.append(1e3 * (time.perf_counter() - t0) / len(records))
+        print("autodecode flow: %d grasp3 scenes, %d steps, %d + %d samples per head: %.1f ms per sample (runs %.1f .. %.1f; wall, meshes read and "
+              "sampled, code written); %s" % (len(records), records[0]["steps"], ad.SAMPLE_DEFAULTS["near"], ad.SAMPLE_DEFAULTS["uniform"],
+                                              float(np.median(per)), min(per), max(per), ad.summary_line(records)))
 
 
 if __name__ == "__main__":

@@ -4,10 +4,11 @@ one-sample fits (fit.fit_code, the way before the batched call), and the autodec
   1. B in {1, 2, 4, 8, 16, 32} samples of M in {1024, 4096, 8192, 32000} targets each (half per head, both heads: the decoder's own
      fields at another code; every sample its own points, code and embedding), STEPS steps, wall time of the whole call after a
      warm-up call, the two ways interleaved, median of REPS rounds.  Both include their one wait at the end.  Printed per cell: ms per
-     sample-step of each way and their ratio, and sum_s grid_s of the batched launch against the part's compute units.
+     sample-step of each way (with its fastest and slowest round) and their ratio, and sum_s grid_s of the batched launch against the
+     part's compute units.
   2. autodecode.run with autodecode.DeviceFitter on eight grasp scenes (meshes by marching cubes of the grasp3 decoder's own fields at
      N = 64), 800 steps, at 8000 targets per sample (3000 + 1000 per head) and at the defaults (12000 + 4000 per head): wall time per
-     sample with --batch 1 and --batch 8, and the host share of it (meshes read, sampled and valued; measured on its own).
+     sample with --batch 1 and --batch 8 (median and range of FLOW_REPS interleaved runs), and the host share of it (meshes read, sampled and valued; measured on its own).
 
     python tools/time_fit_codes.py [--label "<commit>"] > profiles/fit_codes.txt"""
 import argparse
@@ -28,6 +29,7 @@ STEPS = int(os.environ.get("ASDF_TIMING_STEPS", "100"))
 BATCHES = tuple(int(b) for b in os.environ.get("ASDF_TIMING_BATCHES", "1,2,4,8,16,32").split(","))
 LENGTHS = tuple(int(m) for m in os.environ.get("ASDF_TIMING_LENGTHS", "1024,4096,8192,32000").split(","))
 SCENES = 8
+FLOW_REPS = int(os.environ.get("ASDF_TIMING_FLOW_REPS", "3"))
 
 
 def wall(fn):
@@ -86,9 +88,10 @@ def main():
                 for k, fn in ways.items():
                     times[k].append(wall(fn) / (STEPS * B))
             med = {k: float(np.median(v)) for k, v in times.items()}
-            print("M=%-6d B=%-3d fit_code x B %.4f ms / sample-step | fit_codes %.4f ms / sample-step | ratio %.2f x | workgroups %5d of %d "
-                  "compute units (%.2f rounds) | bits equal: %s" % (M, B, med["loop"], med["batch"], med["loop"] / med["batch"], B * grid, num_cus,
-                                                                     B * grid / num_cus, same))
+            print("M=%-6d B=%-3d fit_code x B %.4f (%.4f .. %.4f) ms / sample-step | fit_codes %.4f (%.4f .. %.4f) ms / sample-step | ratio %.2f x | "
+                  "workgroups %5d of %d compute units (%.2f rounds) | bits equal: %s" % (
+                      M, B, med["loop"], min(times["loop"]), max(times["loop"]), med["batch"], min(times["batch"]), max(times["batch"]),
+                      med["loop"] / med["batch"], B * grid, num_cus, B * grid / num_cus, same))
             sys.stdout.flush()
     hip.close()
     if args.skip_flow:
@@ -120,16 +123,20 @@ def main():
             ad.run(specs, fitter, "obman", root, os.path.join(root, "warm"), end=1)
             host = wall(lambda: [fitter._prepare(h, o, {}, np.zeros(256, np.float32)) for _, h, o in pairs]) / len(pairs)
             per, files = {}, {}
-            for batch in (1, 8):
-                out = os.path.join(root, "codes_%d_%d" % (near, batch))
-                t0 = time.perf_counter()
-                _, records = ad.run(specs, fitter, "obman", root, out, batch=batch)
-                per[batch] = 1e3 * (time.perf_counter() - t0) / len(records)
-                files[batch] = [open(os.path.join(out, n), "rb").read() for n in sorted(os.listdir(out))]
-            print("autodecode flow: %d grasp3 scenes, %d steps, %d + %d samples per head (%d targets per sample): --batch 1 %.1f ms per sample, "
-                  "--batch 8 %.1f ms per sample (%.2f x), of which the host's share (meshes read, sampled and valued) %.1f ms per sample; "
-                  "files byte-identical: %s; %s" % (len(records), records[0]["steps"], near, uniform, 2 * (near + uniform), per[1], per[8],
-                                                  per[1] / per[8], host, files[1] == files[8], ad.summary_line(records)))
+            runs = {1: [], 8: []}
+            for _ in range(FLOW_REPS):
+                for batch in (1, 8):
+                    out = os.path.join(root, "codes_%d_%d" % (near, batch))
+                    t0 = time.perf_counter()
+                    _, records = ad.run(specs, fitter, "obman", root, out, batch=batch)
+                    runs[batch].append(1e3 * (time.perf_counter() - t0) / len(records))
+                    files[batch] = [open(os.path.join(out, n), "rb").read() for n in sorted(os.listdir(out))]
+            per = {batch: float(np.median(v)) for batch, v in runs.items()}
+            print("autodecode flow: %d grasp3 scenes, %d steps, %d + %d samples per head (%d targets per sample): --batch 1 %.1f (%.1f .. %.1f) ms "
+                  "per sample, --batch 8 %.1f (%.1f .. %.1f) ms per sample (%.2f x), of which the host's share (meshes read, sampled and valued) "
+                  "%.1f ms per sample; files byte-identical: %s; %s" % (
+                      len(records), records[0]["steps"], near, uniform, 2 * (near + uniform), per[1], min(runs[1]), max(runs[1]), per[8], min(runs[8]),
+                      max(runs[8]), per[1] / per[8], host, files[1] == files[8], ad.summary_line(records)))
             sys.stdout.flush()
 
 
