@@ -45,6 +45,8 @@ EXPORTS = (
     "asdf_fit_code",
     # (the same loop over a batch of samples, csrc/k1vb_kernels.hip: looked up by name in the same way)
     "asdf_fit_codes_workspace_bytes", "asdf_fit_codes",
+    # (the MANO hand layer, csrc/mano.hip: looked up by name in the same way)
+    "asdf_mano_workspace_bytes", "asdf_mano_prepare", "asdf_mano_forward", "asdf_mano_backward",
 )
 FIT_STATE_BYTES = 5120  # ASDF_FIT_STATE_BYTES
 MATH_F32, MATH_F16X3 = 0, 1
@@ -168,6 +170,10 @@ def lib():
     L.asdf_mesh_sdf_workspace_bytes.argtypes = [i32, i64, ctypes.POINTER(ctypes.c_size_t)]
     L.asdf_mesh_sdf_prepare.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     L.asdf_mesh_sdf_points.argtypes = [vp, i32, vp, i64] + [vp] * 4 + [vp, vp]
+    L.asdf_mano_workspace_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    L.asdf_mano_prepare.argtypes = [i32, i32] + [vp] * 8 + [vp, ctypes.c_size_t, vp]
+    L.asdf_mano_forward.argtypes = [vp, ctypes.c_size_t, i32, i32, i32, vp, vp, vp, i32] + [vp] * 5 + [vp]
+    L.asdf_mano_backward.argtypes = [vp, ctypes.c_size_t, i32, i32, i32, vp, vp, vp, i32] + [vp] * 6 + [vp]
     L.asdf_mc_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.asdf_mc_count.argtypes = [vp, i32, i32, i32, ctypes.c_double, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
                                 ctypes.POINTER(ctypes.c_uint32), vp]

@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libalignsdf_hip.so")
-SOURCES = ["decoder.hip", "k1_kernels.hip", "k1pa_kernels.hip", "k1g_kernels.hip", "k1v_kernels.hip", "k1vb_kernels.hip", "k1t_kernels.hip", "k1p_kernels.hip", "k1_cls_kernels.hip", "k1h_kernels.hip", "k1hw_kernels.hip", "k1h_nerf_kernels.hip", "k1s_kernels.hip", "k1s_nerf_kernels.hip", "mc33.hip", "icp.hip", "mesh_cc.hip", "surface_sample.hip", "interaction.hip", "mesh_sdf.hip"]
+SOURCES = ["decoder.hip", "k1_kernels.hip", "k1pa_kernels.hip", "k1g_kernels.hip", "k1v_kernels.hip", "k1vb_kernels.hip", "k1t_kernels.hip", "k1p_kernels.hip", "k1_cls_kernels.hip", "k1h_kernels.hip", "k1hw_kernels.hip", "k1h_nerf_kernels.hip", "k1s_kernels.hip", "k1s_nerf_kernels.hip", "mc33.hip", "icp.hip", "mesh_cc.hip", "surface_sample.hip", "interaction.hip", "mesh_sdf.hip", "mano.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # (-ffp-contract=off, and the toolchain's default of correctly rounded fp32 division and square root - never pass
 # -fno-hip-fp32-correctly-rounded-divide-sqrt: the Adam step of k1v_kernels.hip equals fit.adam_step_host bit for bit only with both)

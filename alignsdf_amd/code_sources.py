@@ -81,9 +81,12 @@ def synthetic_code_source(tag="nerf3", device="cuda", on_host=True):
     return source
 
 
-def npz_code_source(code_dir, device="cuda", on_host=True):
+def npz_code_source(code_dir, device="cuda", on_host=True, mano_model=None):
     """Codes saved by an external encoder run: <code_dir>/<sample>.npz with `latent` [1,256] and optionally
-    `global_trans` [1,16,4,4], `rot_center` [1,1,3], `obj_trans` [1,4,4]."""
+    `global_trans` [1,16,4,4], `rot_center` [1,1,3], `obj_trans` [1,4,4].  A file may hold MANO parameters instead of the first two -
+    `mano_pose` [1, 3 + ncomps] and `mano_shape` [1,10]: with `mano_model` (a mano.ManoModel) the source makes global_trans and
+    rot_center from them by mano.mano_torch ON THE HOST - hip_decoder.kinematic_affine consumes these matrices on the host, a device
+    tensor there would be a synchronising read.  Such a file without a model is an error; a file with global_trans is read as ever."""
     up = _code_converter(device, on_host)
 
     def source(name, index):
@@ -93,6 +96,15 @@ def npz_code_source(code_dir, device="cuda", on_host=True):
         if "global_trans" in z.files:
             mano = {"global_trans": up(np.asarray(z["global_trans"], dtype=np.float32)),
                     "rot_center": up(np.asarray(z["rot_center"], dtype=np.float32))}
+        elif "mano_pose" in z.files:
+            if mano_model is None:
+                raise ValueError("%s.npz holds mano_pose / mano_shape instead of global_trans: a MANO model is needed (--mano_model)" % name)
+            from .mano import mano_torch
+            pose = torch.from_numpy(np.asarray(z["mano_pose"], dtype=np.float32).reshape(1, -1))
+            shape = torch.from_numpy(np.asarray(z["mano_shape"], dtype=np.float32).reshape(1, 10))
+            with torch.no_grad():
+                _, _, _, global_trans, center = mano_torch(mano_model, pose, shape, center_idx=0)
+            mano = {"global_trans": up(global_trans.numpy()), "rot_center": up(center.numpy())}
         if "obj_trans" in z.files:
             obj = {"obj_trans": up(np.asarray(z["obj_trans"], dtype=np.float32))}
         return lat, mano, obj
@@ -102,7 +114,11 @@ def npz_code_source(code_dir, device="cuda", on_host=True):
 def code_source_from_args(args, specs, parser):
     """--codes DIR | --synthetic; neither is an error (there is no silent default)."""
     if args.code_dir:
-        return npz_code_source(args.code_dir)
+        model = None
+        if getattr(args, "mano_model", None):
+            from .mano import ManoModel
+            model = ManoModel.from_npz(args.mano_model)
+        return npz_code_source(args.code_dir, mano_model=model)
     if getattr(args, "synthetic", False):
         return synthetic_code_source("nerf3" if specs["PointFeatSize"] == 3 else "both9")
     parser.error("no latent codes: pass --codes <dir of <sample>.npz written by the encoder run> (or --synthetic for a benchmark run)")

@@ -225,6 +225,7 @@ def main(argv=None):
     p.add_argument("--label", dest="label_out", action="store_true")
     p.add_argument("--viz", dest="viz", action="store_true")
     p.add_argument("--codes", dest="code_dir", default=None, help="directory of precomputed <sample>.npz codes")
+    p.add_argument("--mano_model", default=None, help="MANO model .npz (tools/mano_pkl_to_npz.py): codes files may then hold mano_pose / mano_shape instead of global_trans / rot_center")
     p.add_argument("--synthetic", action="store_true", help="deterministic synthetic codes (tests / benchmarks only: the meshes mean nothing)")
     p.add_argument("--allow_missing_gt", action="store_true", help="eval mode: write unaligned meshes when a ground-truth mesh is missing instead of aborting")
     p.add_argument("--cube_dim", type=int, default=128, help="grid resolution (reference CLI hard-codes 128, reconstruct.py:178)")

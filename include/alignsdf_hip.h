@@ -686,6 +686,52 @@ int asdf_mesh_sdf_prepare(const float* verts_dev, int32_t num_verts, const int32
 int asdf_mesh_sdf_points(const void* workspace_dev, int32_t num_faces, const float* xyz_dev, int64_t M, float* sdf_dev,
                          float* winding_dev, int32_t* face_dev, float* closest_dev, void* scratch_dev, void* stream);
 
+/* ---- The MANO hand layer, forward and reverse (csrc/mano.hip): manopth/manolayer.py:126-271 in the one configuration
+ * networks/manobranch.py builds - PCA pose coefficients behind three global axis-angle values, rodrigues_layer.py:43-54.  Plain device
+ * arrays in and out, no decoder, nothing waits for the stream, nothing is allocated.
+ *
+ * THE MODEL, V vertices (1 .. ASDF_MANO_MAX_VERTS; MANO's is 778), fp32: v_template [V][3], shapedirs [V][3][10], posedirs [V][3][135],
+ * J_regressor [16][V] (dense), weights [V][16], hands_mean [45], comps [ncomps][45] (ncomps in 1..45), tips int32 [5] (vertex ids; one
+ * outside [0, V) is clamped into it).  The 16 joints and their tree are fixed: parents -1,0,1,2,0,4,5,0,7,8,0,10,11,0,13,14.
+ *
+ * THE RULE, for pose [3 + ncomps] and shape [10], all arithmetic in fp32 without contraction:
+ *   hand_pose   = pose[3..] . comps                                [45]   (the reference layer's third return: without the mean)
+ *   full        = [pose[0..2], hands_mean + hand_pose]             [48]   axis-angle a_j of joint j = full[3j..3j+2]
+ *   R_j         by the quaternion route: n = |a + 1e-8| (the constant added to every component - it keeps a zero rotation finite and
+ *               differentiable), q = (cos(n/2), sin(n/2) a / n), q <- q / |q|, R_j the rotation of the unit quaternion q
+ *   v_shaped    = shapedirs . shape + v_template;   J = J_regressor . v_shaped   (the regressor is folded into template and directions at
+ *               prepare time with fp64 sums: J = jt + js . shape, ten terms)
+ *   v_posed     = v_shaped + posedirs . m,   m [135] = (R_j - I) of j = 1..15, row-major, joint after joint
+ *   G_0 = [R_0 | J_0],   G_j = G_parent(j) [R_j | J_j - J_parent(j)]        (global_trans: th_results_global)
+ *   A_j         = G_j with G_j's rotation applied to J_j taken off its translation   (th_results2)
+ *   vert_v      = (sum_j weights[v][j] A_j) [v_posed_v; 1]
+ *   joints      the 16 translations of G followed by the 5 tip vertices, reordered by 0,13,14,15,16,1,2,3,17,4,5,6,18,10,11,12,19,7,8,9,20
+ *   then        trans_dev given: verts and joints + trans;  else center_idx >= 0: center = joints[center_idx], verts and joints - center;
+ *               else neither.
+ * Every sum has one owner and a fixed order (no atomics): two calls agree in every bit, and a sample's results depend neither on B nor
+ * on its place in the batch.  One workgroup per sample, intermediates in LDS.
+ *
+ * asdf_mano_workspace_bytes: the bytes asdf_mano_prepare fills for a model of num_verts vertices used with ncomps components.
+ * asdf_mano_prepare, once per (model, ncomps): after it nothing reads the model arrays again.  workspace_dev 16-byte aligned.
+ * asdf_mano_forward: pose_dev [B][3 + ncomps], shape_dev [B][10], trans_dev [B][3] or NULL; outputs verts_dev [B][V][3], joints_dev [B][21][3],
+ *   global_trans_dev [B][16][4][4], center_dev [B][3] (written only when the centre is taken), hand_pose_dev [B][45]; each may be NULL.
+ * asdf_mano_backward: the same inputs and the cotangents d_verts_dev [B][V][3], d_joints_dev [B][21][3], d_global_trans_dev [B][16][4][4]
+ *   (its constant last rows are ignored), d_center_dev [B][3] (ignored unless the centre is taken), each NULL for zero; recomputes the
+ *   forward in LDS and writes d_pose_dev [B][3 + ncomps] and d_shape_dev [B][10].  trans_dev only selects the mode; it gets no gradient.
+ * B == 0 is ASDF_OK.  ASDF_EINVAL: num_verts or ncomps outside their ranges, B < 0, center_idx outside [-1, 20] (-1: none), a NULL
+ *   required or a misaligned pointer.  ASDF_ENOSPC: workspace_bytes below asdf_mano_workspace_bytes. */
+#define ASDF_MANO_MAX_VERTS 1024
+int asdf_mano_workspace_bytes(int32_t num_verts, int32_t ncomps, size_t* bytes);
+int asdf_mano_prepare(int32_t num_verts, int32_t ncomps, const float* v_template_dev, const float* shapedirs_dev, const float* posedirs_dev,
+                      const float* j_regressor_dev, const float* weights_dev, const float* hands_mean_dev, const float* comps_dev,
+                      const int32_t* tips_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int asdf_mano_forward(const void* workspace_dev, size_t workspace_bytes, int32_t num_verts, int32_t ncomps, int32_t B, const float* pose_dev,
+                      const float* shape_dev, const float* trans_dev, int32_t center_idx, float* verts_dev, float* joints_dev,
+                      float* global_trans_dev, float* center_dev, float* hand_pose_dev, void* stream);
+int asdf_mano_backward(const void* workspace_dev, size_t workspace_bytes, int32_t num_verts, int32_t ncomps, int32_t B, const float* pose_dev,
+                       const float* shape_dev, const float* trans_dev, int32_t center_idx, const float* d_verts_dev, const float* d_joints_dev,
+                       const float* d_global_trans_dev, const float* d_center_dev, float* d_pose_dev, float* d_shape_dev, void* stream);
+
 /* ---- Translate + scale ICP of the reference's eval mode: ICP_T_S.run_icp_f (deep_sdf/metrics/icp_trans_scale.py:33-113),
  * called from utils/mesh.py:385-395.  src_dev [ns][3] are the ALREADY NORMALISED source samples (sample_mesh :25-31),
  * tgt_dev [nt][3] the target samples, both fp64 on the device.  Runs until the reference's stopping rules fire
