@@ -28,7 +28,8 @@
 // there.  This header holds its own copy of the stage and of the body because the 32-wide forms sit at the 512-register limit: with
 // the W paths as a template parameter of their body - every one of them `if constexpr` - the CombinedDecoder form took 60 B and the
 // subset form 20 B of scratch.  The copy is specialised: two planes, one 32-point group, K = 4 point features, one output, the
-// shipped schedule (deferred epilogue parts in three pieces, one LDS-DMA piece per K-block, preloads half a tile ahead).
+// shipped schedule (deferred epilogue parts in five steps, one behind each MFMA of a record; one LDS-DMA piece per K-block; preloads
+// half a tile ahead).
 #pragma once
 #include "sdf_mlp_f16_kernel.h"
 
@@ -63,16 +64,19 @@ __device__ __forceinline__ f32x16 load_bias16w(const float* tile_words, int lane
   return r;
 }
 
-// The accumulator is four independent quads: pinned one by one (see pin_acc) - the 512-bit constraint of the 32-wide form makes the
-// compiler gather them into one aligned tuple through 16 v_accvgpr_read / write pairs per tile.
-__device__ __forceinline__ void pin_acc_w(f32x16& acc) {
-#pragma unroll
-  for (int o = 0; o < 16; o += 4) {
-    f32x4 q;
-    q[0] = acc[o]; q[1] = acc[o + 1]; q[2] = acc[o + 2]; q[3] = acc[o + 3];
-    asm volatile("" : "+a"(q));
-    acc[o] = q[0]; acc[o + 1] = q[1]; acc[o + 2] = q[2]; acc[o + 3] = q[3];
-  }
+// relu of ONE register of a finished accumulator, read where this statement stands.  The accumulator is four independent quads (see
+// pin_acc for what a pin is for; the 512-bit pin of the 32-wide form makes the compiler gather them into one aligned tuple through 16
+// v_accvgpr_read / write pairs per tile) and a deferred epilogue step pins the ONE quad it reads, because the compiler places a read
+// AT the pin in front of it: one pin of the whole accumulator per record put both reads of a part, and an s_nop, into the record's
+// first gap.  (Reading through inline assembly instead - no pin, no s_nop - costs AGPRs: the tile prologue's addresses then go to
+// scratch and come back between the MFMAs, 14 reloads per tile body.)
+__device__ __forceinline__ float relu_acc_w(f32x16& acc, int i) {
+  const int o = i & ~3;
+  f32x4 q;
+  q[0] = acc[o]; q[1] = acc[o + 1]; q[2] = acc[o + 2]; q[3] = acc[o + 3];
+  asm volatile("" : "+a"(q));
+  acc[o] = q[0]; acc[o + 1] = q[1]; acc[o + 2] = q[2]; acc[o + 3] = q[3];
+  return __int_as_float(max(__float_as_int(acc[i]), 0));
 }
 
 // One LDS-DMA piece with M0 written WITHOUT saving and restoring it around the instruction (3 instead of 5 instructions per piece).
@@ -98,10 +102,76 @@ __device__ __forceinline__ void dma_piece_w(const float* src, unsigned dst) {
 #endif
 }
 
+// A deferred epilogue part (split_part<2, 1, true> of sdf_mlp_f16_kernel.h: element e of the four planes, 9 VALU instructions) in
+// FIVE steps, one behind each of a record's first five MFMAs - at most two instructions per gap, which is what a 16-clock MFMA hides
+// beside its own issue: [0] / [1] one accumulator read + ReLU each (rr carries them), [2] the two high planes, [3] the two low
+// planes, [4] the running maximum.  The same instructions on the same values as split_part's three pieces (the maximum commutes).
+// A half-register write needs two wait states in front of its first read: the sibling's instruction and the MFMA between [2] and [3].
+__device__ __forceinline__ void split_step_w(f32x16& acc, float mul, h8& hi0, h8& lo0, h8& hi1, h8& lo1, float& amax, int e, int step,
+                                             float* rr) {
+  if (step == 0) { rr[0] = relu_acc_w(acc, e); return; }
+  if (step == 1) { rr[1] = relu_acc_w(acc, 8 + e); return; }
+  if (step == 4) { asm("v_max3_f32 %0, %0, %1, %2" : "+v"(amax) : "v"(rr[0]), "v"(rr[1])); return; }
+  if (step != 2 && step != 3) return;
+  const float r0 = rr[0], r1 = rr[1];
+  u32x4 H0 = __builtin_bit_cast(u32x4, hi0), L0 = __builtin_bit_cast(u32x4, lo0);
+  u32x4 H1 = __builtin_bit_cast(u32x4, hi1), L1 = __builtin_bit_cast(u32x4, lo1);
+  unsigned a = H0[e >> 1], b = L0[e >> 1], c = H1[e >> 1], d = L1[e >> 1];
+  if (step == 2) {
+    if (e & 1)
+      asm("v_fma_mixhi_f16 %0, %2, %4, 0\n\t"
+          "v_fma_mixhi_f16 %1, %3, %4, 0"
+          : "+v"(a), "+v"(c) : "v"(r0), "v"(r1), "v"(mul));
+    else        // (the even element defines the register: nothing of the previous tile's value is read)
+      asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
+          "v_fma_mixlo_f16 %1, %3, %4, 0"
+          : "=&v"(a), "=&v"(c) : "v"(r0), "v"(r1), "v"(mul));
+    H0[e >> 1] = a; H1[e >> 1] = c;
+    hi0 = __builtin_bit_cast(h8, H0); hi1 = __builtin_bit_cast(h8, H1);
+  } else {
+    if (e & 1)
+      asm("v_fma_mixhi_f16 %0, %2, %4, -%5 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+          "v_fma_mixhi_f16 %1, %3, %4, -%6 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+          : "+v"(b), "+v"(d) : "v"(r0), "v"(r1), "v"(mul), "v"(a), "v"(c));
+    else
+      asm("v_fma_mixlo_f16 %0, %2, %4, -%5 op_sel_hi:[0,0,1]\n\t"
+          "v_fma_mixlo_f16 %1, %3, %4, -%6 op_sel_hi:[0,0,1]"
+          : "=&v"(b), "=&v"(d) : "v"(r0), "v"(r1), "v"(mul), "v"(a), "v"(c));
+    L0[e >> 1] = b; L1[e >> 1] = d;
+    lo0 = __builtin_bit_cast(h8, L0); lo1 = __builtin_bit_cast(h8, L1);
+  }
+}
+
+// s_waitcnt lgkmcnt(n) with the other counters left open, as the compiler's own instruction (it merges with the waits it computes)
+__device__ __forceinline__ void wait_lds_w(int n) {
+  switch (n) {
+    case 2: __builtin_amdgcn_s_waitcnt(0xc27f); break;
+    case 3: __builtin_amdgcn_s_waitcnt(0xc37f); break;
+    case 4: __builtin_amdgcn_s_waitcnt(0xc47f); break;
+    case 5: __builtin_amdgcn_s_waitcnt(0xc57f); break;
+    case 6: __builtin_amdgcn_s_waitcnt(0xc67f); break;
+    case 7: __builtin_amdgcn_s_waitcnt(0xc77f); break;
+    case 8: __builtin_amdgcn_s_waitcnt(0xc87f); break;
+    default: break;
+  }
+}
+
+// Shader-clock stamps of a stage's record classes: nothing in the shipped kernels (an empty object); the diagnostic build of
+// tools/k1h_ablate.hip (-DSTAMP=1) defines ASDF16_W_STAMPS and its own StageStamps16w in front of this header.
+#ifndef ASDF16_W_STAMPS
+struct StageStamps16w {
+  __device__ __forceinline__ void at(int) {}         // in front of record kb (its A-fragment reads included)
+  __device__ __forceinline__ void flush(int) {}      // behind the stage; the argument is the stage's kind (0 / 1: first / second stage of a
+};                                                   // layer-1 / layer-3 tile, 2: a layer-2 tile)
+#endif
+
 // One stage = 16 records of one 32-feature output tile; KB = records per tile (32: layers 1 / 3, 16: layer 2), Q = the stage's
 // index within the tile.  The structure of stage16 (sdf_mlp_f16_kernel.h): on entry (ah, al) hold the A fragments of the stage's
 // first record(s), on exit those of the next stage in stream order; every record is one scheduling region
-//     [A-fragment reads of record kb + PREFETCH, pre(kb)]  fence  [2 MFMAs, piece 0] [2 MFMAs, piece 1] [2 MFMAs, DMA piece, piece 2]
+//     [A-fragment reads of record kb + PREFETCH, pre(kb)]  fence  wait  [MFMA, step 0] ... [MFMA, DMA piece, step 4] [MFMA, step 5]
+// (six regions of one MFMA and a step of at most two instructions - and the compiler's s_nop 0 in front of an accumulator read: with
+// one wave per SIMD a 16-clock MFMA leaves the vector issue 8 clocks, two 4-clock instructions - profiles/k1hw_record_budget.txt).
+// pre(kb) returns the number of LDS reads it issued.
 // The order of the six MFMAs is what decides this kernel's speed: a group's three MFMAs - (W_hi, x_lo), (W_lo, x_hi), (W_hi, x_hi),
 // small terms first - sit back to back, and the groups take turns in SNAKE order from record to record, so that five of six MFMAs
 // continue the accumulator of the MFMA right in front of them (the matrix pipe forwards it).  Product sum outer / group inner - no
@@ -126,8 +196,10 @@ __device__ __forceinline__ void stage16w(f32x16& acc, const h8 (&xh)[KB], const 
   h8 bufh[kS16Kb + PF], bufl[kS16Kb + PF];
 #pragma unroll
   for (int i = 0; i < PF; ++i) { bufh[i] = ah[i]; bufl[i] = al[i]; }
+  StageStamps16w stamps;
 #pragma unroll
   for (int kb = 0; kb < kS16Kb; ++kb) {
+    stamps.at(kb);
     if (kb == BKB && !(ABL & 1)) {
       // my pieces of stage (this + 1) were issued 2.5 stages ago; only those of (this + 2) may stay in flight
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -135,24 +207,32 @@ __device__ __forceinline__ void stage16w(f32x16& acc, const h8 (&xh)[KB], const 
     }
     bufh[kb + PF] = kb + PF < kS16Kb ? cur[((kb + PF) * 2 + 0) * 64] : nxt[((kb + PF - kS16Kb) * 2 + 0) * 64];
     bufl[kb + PF] = kb + PF < kS16Kb ? cur[((kb + PF) * 2 + 1) * 64] : nxt[((kb + PF - kS16Kb) * 2 + 1) * 64];
-    pre(kb);
+    const int pre_reads = pre(kb);      // (LDS read instructions it issued)
     __builtin_amdgcn_sched_barrier(0);
+    // ONE wait for both A fragments of the record (read one record ago: everything but this region's own reads has to be back)
+    // instead of one in front of each of the first two MFMAs
+    wait_lds_w(2 + pre_reads);
     // record ri of the tile: feature half fh, K32-block j (see the header); B operands xh / xl[2 j + g], accumulator quads 4 fh, 8 + 4 fh
     const int ri = Q * kS16Kb + kb;
     const int xb = KB == 32 ? 2 * (ri % 16) : (ri & ~1), o = (KB == 32 ? ri / 16 : (ri & 1)) * 4;
     const bool snake = ri & 1;
     const int xa = xb + (snake ? 1 : 0), xc = xb + (snake ? 0 : 1);      // the group that goes first / second in this record
+    // every MFMA is its own scheduling region with its step of the epilogue part behind it
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < 6; ++j) {
       f32x4 s0 = acc_get4(acc, o), s1 = acc_get4(acc, 8 + o);
       f32x4& sa = snake ? s1 : s0;
       f32x4& sb = snake ? s0 : s1;
-      if (j == 0) { sa = ASDF_MFMA16W(bufh[kb], xl[xa], sa); sa = ASDF_MFMA16W(bufl[kb], xh[xa], sa); }
-      if (j == 1) { sa = ASDF_MFMA16W(bufh[kb], xh[xa], sa); sb = ASDF_MFMA16W(bufh[kb], xl[xc], sb); }
-      if (j == 2) { sb = ASDF_MFMA16W(bufl[kb], xh[xc], sb); sb = ASDF_MFMA16W(bufh[kb], xh[xc], sb); }
+      if (j == 0) sa = ASDF_MFMA16W(bufh[kb], xl[xa], sa);
+      if (j == 1) sa = ASDF_MFMA16W(bufl[kb], xh[xa], sa);
+      if (j == 2) sa = ASDF_MFMA16W(bufh[kb], xh[xa], sa);
+      if (j == 3) sb = ASDF_MFMA16W(bufh[kb], xl[xc], sb);
+      if (j == 4) sb = ASDF_MFMA16W(bufl[kb], xh[xc], sb);
+      if (j == 5) sb = ASDF_MFMA16W(bufh[kb], xh[xc], sb);
       acc_set4(acc, o, s0); acc_set4(acc, 8 + o, s1);
-      // one DMA piece per record, behind its LAST MFMA pair - the gap that carries the least of a deferred epilogue part
-      const int m = j == 2 ? kb - BKB : -1;
+      __builtin_amdgcn_sched_barrier(0);      // (the MFMA FIRST: left to the scheduler, a step in front of its MFMA doubles the previous gap)
+      // one DMA piece per record, behind its fifth MFMA - the gap that carries one instruction of a deferred epilogue part
+      const int m = j == 4 ? kb - BKB : -1;
       if (!(ABL & 1) && !(ABL & 32) && m >= 0 && m < SG::kPieces) {
         if (m == 0) dma_piece_w<0>(src, dst);
         else if (m == 1) dma_piece_w<1>(src, dst);
@@ -164,11 +244,13 @@ __device__ __forceinline__ void stage16w(f32x16& acc, const h8 (&xh)[KB], const 
         else dma_piece_w<7>(src, dst);
         __builtin_amdgcn_sched_barrier(0);
       }
-      epi(kb, j);      // piece j of the record's deferred epilogue part
+      epi(kb, j);      // step j of the record's deferred epilogue part
       __builtin_amdgcn_sched_barrier(0);
     }
     __builtin_amdgcn_sched_barrier(0);
   }
+  stamps.at(kS16Kb);
+  stamps.flush(KB == 16 ? 2 : Q);
 #pragma unroll
   for (int i = 0; i < PF; ++i) { ah[i] = bufh[kS16Kb + i]; al[i] = bufl[kS16Kb + i]; }
 }
@@ -333,8 +415,8 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
 #define ASDF_STAGE16W(KB, Q, SLOT, ACC, XH, XL, SIDX, PRE, EPI) \
   stage16w<KB, Q, SLOT, ABL>(ACC, XH, XL, ring, src_of((SIDX) + 3), lds_ring_base, lane, wave, ah, al, PRE, EPI)
 
-      // (the second argument of an epilogue callback is the PIECE of the part - stage16w calls it behind each of the record's three
-      // MFMA pairs - and `er` carries a part's two ReLUs from piece to piece)
+      // (the second argument of an epilogue callback is the STEP of the part - stage16w calls it behind each of the record's six
+      // MFMAs - and `er` carries a part's two ReLUs from step to step)
       float er[2] = {0.0f, 0.0f};
       // ---- layer 1: 512 -> 256; epilogue of tile t-1 rides in tile t
       h8 h1h[2 * kTilesL1], h1l[2 * kTilesL1];
@@ -342,31 +424,32 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
 #pragma unroll
       for (int t = 0; t < kTilesL1; ++t) {
         f32x16& acc = acc1[t & 1];
-        auto pre = [&](int kb) {       // first stage: the layer-0 tile of the NEXT record's epilogue slot
+        auto pre = [&](int kb) -> int {       // first stage: the layer-0 tile of the NEXT record's epilogue slot
           const int c = kb - kEpiShift;
-          if (t == 0 && c >= 0 && c + 1 < kEpiChunks) l0_load(kL0Front + c + 1);
+          if (t == 0 && c >= 0 && c + 1 < kEpiChunks) { l0_load(kL0Front + c + 1); return 6; }
+          return 0;
         };
         auto epi = [&](int kb, int g) {
           const int c = kb - kEpiShift;
           if (c < 0 || c >= kEpiChunks) return;
           if (t == 0) {
-            // a whole layer-0 tile per record: its fp32 MFMAs behind the first pair, its eight parts over the three gaps (3 + 3 + 2)
+            // a whole layer-0 tile per record: its fp32 MFMAs behind the first MFMA, its eight parts behind the other five (2 + 2 + 2 + 1 + 1)
             const int T = kL0Front + c;
             if (g == 0) pt_mfma(acc0[T & 1], pf0[T & 1]);
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-              if (e / 3 == g) split_part<2, 1, true>(acc0[T & 1], acc0[T & 1], mul0, h0h[2 * T], h0l[2 * T], h0h[2 * T + 1], h0l[2 * T + 1], amax, e);
+              if ((e < 6 ? 1 + e / 2 : e - 2) == g)
+                split_part<2, 1, true>(acc0[T & 1], acc0[T & 1], mul0, h0h[2 * T], h0l[2 * T], h0h[2 * T + 1], h0l[2 * T + 1], amax, e);
             return;
           }
           if (ABL & 4) { asm volatile("" :: "v"(acc1[(t - 1) & 1])); return; }
-          if (g == 0) pin_acc_w(acc1[(t - 1) & 1]);
-          split_part<2, 1, true>(acc1[(t - 1) & 1], acc1[(t - 1) & 1], mul1, h1h[2 * (t - 1)], h1l[2 * (t - 1)], h1h[2 * (t - 1) + 1],
-                                 h1l[2 * (t - 1) + 1], amax1, c, -1, g, er);
+          split_step_w(acc1[(t - 1) & 1], mul1, h1h[2 * (t - 1)], h1l[2 * (t - 1)], h1h[2 * (t - 1) + 1], h1l[2 * (t - 1) + 1], amax1, c, g, er);
         };
-        auto pre_last = [&](int c) {   // last stage: bias row (and point fragments) of the next tile
-          if (c != kPreKb) return;
-          if (t + 1 < kTilesL1) acc1[(t + 1) & 1] = bias_at(CL::kB1, t + 1);
-          else { acc2[0] = bias_at(CL::kC2, 0); load_pf2(0); }
+        auto pre_last = [&](int c) -> int {   // last stage: bias row (and point fragments) of the next tile
+          if (c != kPreKb) return 0;
+          if (t + 1 < kTilesL1) { acc1[(t + 1) & 1] = bias_at(CL::kB1, t + 1); return 4; }
+          acc2[0] = bias_at(CL::kC2, 0); load_pf2(0);
+          return 6;
         };
         if (t & 1) {
           ASDF_STAGE16W(32, 0, 2, acc, h0h, h0l, t * 2 + 0, pre, epi);
@@ -390,19 +473,17 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
           if (c < 0 || c >= kEpiChunks) return;
           if (ABL & 4) { asm volatile("" :: "v"(acc2[(t + 1) & 1]), "v"(acc1[1])); return; }
           if (t > 0) {
-            if (g == 0) pin_acc_w(acc2[(t - 1) & 1]);
-            split_part<2, 1, true>(acc2[(t - 1) & 1], acc2[(t - 1) & 1], mul2, h2h[2 * (t - 1)], h2l[2 * (t - 1)], h2h[2 * (t - 1) + 1],
-                                   h2l[2 * (t - 1) + 1], amax2, c, -1, g, er);
+            split_step_w(acc2[(t - 1) & 1], mul2, h2h[2 * (t - 1)], h2l[2 * (t - 1)], h2h[2 * (t - 1) + 1], h2l[2 * (t - 1) + 1], amax2, c, g, er);
           } else {
-            if (g == 0) pin_acc_w(acc1[(kTilesL1 - 1) & 1]);
-            split_part<2, 1, true>(acc1[(kTilesL1 - 1) & 1], acc1[(kTilesL1 - 1) & 1], mul1, h1h[2 * kTilesL1 - 2], h1l[2 * kTilesL1 - 2],
-                                   h1h[2 * kTilesL1 - 1], h1l[2 * kTilesL1 - 1], amax1, c, -1, g, er);      // the last K32-block's operands: consumed from record 14 on
+            split_step_w(acc1[(kTilesL1 - 1) & 1], mul1, h1h[2 * kTilesL1 - 2], h1l[2 * kTilesL1 - 2], h1h[2 * kTilesL1 - 1], h1l[2 * kTilesL1 - 1],
+                         amax1, c, g, er);      // the last K32-block's operands: consumed from record 14 on
           }
         };
-        auto pre_last = [&](int c) {
-          if (c != kPreKb) return;
-          if (t + 1 < kTilesHidden) { acc2[(t + 1) & 1] = bias_at(CL::kC2, t + 1); load_pf2(t + 1); }
-          else acc3[0] = bias_at(CL::kB3, 0);
+        auto pre_last = [&](int c) -> int {
+          if (c != kPreKb) return 0;
+          if (t + 1 < kTilesHidden) { acc2[(t + 1) & 1] = bias_at(CL::kC2, t + 1); load_pf2(t + 1); return 6; }
+          acc3[0] = bias_at(CL::kB3, 0);
+          return 4;
         };
         constexpr int S0 = 256 / kS16Kb;         // stages of layer 1
         ASDF_STAGE16W(16, 0, SLOT, acc, h1h, h1l, S0 + t, pre_last, epi);      // one stage per tile
@@ -428,32 +509,39 @@ __device__ __forceinline__ void sdf_mlp_f16w_body(const DecodeParams& p) {
           else partg = fmaf(v, w4c[r], partg);
         }
       };
+      // ... under the MFMAs in four steps: [0] / [2] read + ReLU of register 2 c / 2 c + 1 (er carries it), [1] / [3] its product
+      auto dot_w4_step = [&](f32x16& a, int c, int step) {
+        const int r = step >> 1;
+        if (!(step & 1)) er[r] = relu_acc_w(a, 2 * c + r);
+        else if (c < 4) part = fmaf(er[r], w4c[r], part);
+        else partg = fmaf(er[r], w4c[r], partg);
+      };
 #pragma unroll
       for (int t = 0; t < kTilesHidden; ++t) {
         f32x16& acc = acc3[t & 1];
-        auto pre = [&](int kb) {       // first stage: w4 of the next epilogue part
+        auto pre = [&](int kb) -> int {       // first stage: w4 of the next epilogue part
           const int c = kb - kEpiShift;
-          if (t > 0 && c >= 0 && c + 1 < kEpiChunks) load_w4(t - 1, c + 1);
+          if (t > 0 && c >= 0 && c + 1 < kEpiChunks) { load_w4(t - 1, c + 1); return 1; }
+          return 0;
         };
         auto epi = [&](int kb, int g) {
           const int c = kb - kEpiShift;
           if (c < 0 || c >= kEpiChunks) return;
           if (ABL & 4) { asm volatile("" :: "v"(acc3[(t + 1) & 1]), "v"(acc2[1])); return; }
-          if (t > 0) {      // piece 0 / 1: one register of the pair each; piece 2: the next pair's weights
-            if (g == 0) pin_acc_w(acc3[(t - 1) & 1]);
-            if (g < 2) dot_w4_part(acc3[(t - 1) & 1], c, g);
-            else next_w4();
+          if (t > 0) {      // steps 0 .. 3: read + ReLU, then the product, of one register of the pair each; step 4: the next pair's weights
+            if (g < 4) dot_w4_step(acc3[(t - 1) & 1], c, g);
+            else if (g == 4) next_w4();
           } else {
-            if (g == 0) pin_acc_w(acc2[(kTilesHidden - 1) & 1]);
-            split_part<2, 1, true>(acc2[(kTilesHidden - 1) & 1], acc2[(kTilesHidden - 1) & 1], mul2, h2h[2 * kTilesHidden - 2],
-                                   h2l[2 * kTilesHidden - 2], h2h[2 * kTilesHidden - 1], h2l[2 * kTilesHidden - 1], amax2, c, -1, g, er);  // the last K32-block's operands: record 15
+            split_step_w(acc2[(kTilesHidden - 1) & 1], mul2, h2h[2 * kTilesHidden - 2], h2l[2 * kTilesHidden - 2], h2h[2 * kTilesHidden - 1],
+                         h2l[2 * kTilesHidden - 1], amax2, c, g, er);  // the last K32-block's operands: record 15
           }
         };
-        auto pre_last = [&](int c) {   // last stage: bias row of the next tile, w4 of the first part of this tile's epilogue
-          if (c != kPreKb) return;
+        auto pre_last = [&](int c) -> int {   // last stage: bias row of the next tile, w4 of the first part of this tile's epilogue
+          if (c != kPreKb) return 0;
           if (t + 1 < kTilesHidden) acc3[(t + 1) & 1] = bias_at(CL::kB3, t + 1);
           load_w4(t, 0);
           next_w4();
+          return t + 1 < kTilesHidden ? 5 : 1;
         };
         constexpr int S0 = 512 / kS16Kb;         // stages of layers 1 and 2
         if (t & 1) {

@@ -1,6 +1,7 @@
 // Timing-only ablation / schedule sweep for the split-half decoder kernel (results are NOT checked here - parity lives
-// in tests/).  Build (per form: -DPLANES=1 [-DGROUPS=2], -DWIDE=1, -DASDF16_STAGE_KB=8):
+// in tests/).  Build (per form: -DPLANES=1 [-DGROUPS=2], -DWIDE=1 [-DSTAMP=1], -DASDF16_STAGE_KB=8):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -w -Ialignsdf_amd/csrc [-DPLANES=1 ...] tools/k1h_ablate.hip -o tools/bin/k1h_x
+// (-DWIDE=1 with the flags of its unit in alignsdf_amd/build_native.py as well: -mllvm -pragma-unroll-threshold=200000)
 // Run:  k1h_x [N] [data]     data = path of a tools/dump_k1h_inputs.py image (the product's real weights + folded
 //                            constants), "zero" (all-zero operands: the DVFS upper bound) or "small" (default: small
 //                            pseudo-random weights that keep every ablation finite)
@@ -12,8 +13,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#ifndef ABL_LIST
-#define ABL_LIST X(0) X(32) X(1) X(16) X(4)
+#ifndef STAMP
+#define STAMP 0         // 1 (with -DWIDE=1) = the diagnostic build: shader-clock stamps of the record classes of the W form's stages
 #endif
 #ifndef PLANES
 #define PLANES 2        // 1 = the one-plane kernel of the box-only coarse sweep
@@ -23,6 +24,41 @@
 #endif
 #ifndef WIDE
 #define WIDE 0          // 1 = the W form (16x16x32 MFMAs; timing only here: it is fed the 32x32x16 image - the same values in another order)
+#endif
+#ifndef ABL_LIST
+#if WIDE && STAMP
+#define ABL_LIST X(0)
+#elif WIDE        // (the W form's record budget: epilogue 4, barrier 16, LDS-DMA 32 and their combinations; 1 = none of the stream)
+#define ABL_LIST X(0) X(4) X(16) X(32) X(20) X(36) X(48) X(52) X(1)
+#else
+#define ABL_LIST X(0) X(32) X(1) X(16) X(4)
+#endif
+#endif
+#if WIDE && STAMP
+// Stamps of the W form's stages (sdf_mlp_f16w_kernel.h: StageStamps16w): s_memtime in front of records 0, 1, 8, 9 and behind record 15
+// of every stage, so that a stage falls into four segments - record 0, records 1 .. 7 (the deferred epilogue parts of a tile's first
+// stage), record 8 (wait + barrier, first LDS-DMA piece), records 9 .. 15 (one LDS-DMA piece each).  Wave 0 of workgroup 0 adds the
+// segments' clocks to g_seg[kind][segment] and counts the stages in g_stages[kind].  A stamp waits for its own result (a scalar memory
+// read returns out of order: any LDS wait behind it would otherwise become lgkmcnt(0)), which costs every segment the same ~50 clocks.
+__device__ unsigned long long g_seg[3][4];
+__device__ unsigned g_stages[3];
+#define ASDF16_W_STAMPS
+namespace asdf {
+struct StageStamps16w {
+  unsigned long long t[5];
+  __device__ __forceinline__ void at(int kb) {
+    const int i = kb == 0 ? 0 : kb == 1 ? 1 : kb == 8 ? 2 : kb == 9 ? 3 : kb == 16 ? 4 : -1;
+    if (i >= 0) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t[i]) :: "memory");
+  }
+  __device__ __forceinline__ void flush(int kind) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) atomicAdd(&g_seg[kind][i], t[i + 1] - t[i]);
+      atomicAdd(&g_stages[kind], 1u);
+    }
+  }
+};
+}  // namespace asdf
 #endif
 #if WIDE
 #include "sdf_mlp_f16w_kernel.h"
@@ -74,13 +110,32 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   const double flop = (double)P * 2 * 3145728.0 / (PLANES == 1 ? 3 : 1);
   printf("GROUPS %d  PLANES %d  PREFETCH %d  BARRIER_KB %d  data %s\n", GROUPS, PLANES, S16<PLANES, GROUPS>::kPrefetch, PLANES == 2 ? kBarrierKb : kBarrierKbP1, data);
+  // K1H_ROUNDS (default 3) passes over the list, so that the forms are timed interleaved: per form the best launch of every pass
+  const int rounds = getenv("K1H_ROUNDS") ? atoi(getenv("K1H_ROUNDS")) : 3;
+  for (int round = 0; round < rounds; ++round) {
 #define X(n) { (void)hipFuncSetAttribute((const void*)k_abl_##n, hipFuncAttributeMaxDynamicSharedMemorySize, kLds); \
     float best = 1e9; double ghz = 0; for (int it = 0; it < 4; ++it) { (void)hipEventRecord(e0); hipLaunchKernelGGL(k_abl_##n, dim3(256), dim3(256), kLds, 0, p); \
       (void)hipEventRecord(e1); (void)hipEventSynchronize(e1); float ms; (void)hipEventElapsedTime(&ms, e0, e1); \
       unsigned long long t[2]; (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_ticks), 16); \
       if (ms < best) { best = ms; ghz = (double)(t[1] - t[0]) / (ms * 1e6); } } \
-    printf("ABL %2d  N=%d  %.3f ms  %.0f TF/s f16 MFMA (%.1f%% of 2516)  wg0 ticks/wall = %.3f GHz  err=%d\n", n, N, best, flop / best / 1e9, flop / best / 1e9 / 25.166, ghz, (int)hipGetLastError()); }
+    printf("pass %d  ABL %2d  N=%d  %.3f ms  %.0f TF/s f16 MFMA (%.1f%% of 2516)  wg0 ticks/wall = %.3f GHz  err=%d\n", round, n, N, best, flop / best / 1e9, flop / best / 1e9 / 25.166, ghz, (int)hipGetLastError()); }
   ABL_LIST
 #undef X
+  }
+#if WIDE && STAMP
+  {
+    // clocks per record of wave 0 of workgroup 0, over every launch above (stamps included: ~50 clocks per segment)
+    unsigned long long seg[3][4]; unsigned stages[3];
+    (void)hipMemcpyFromSymbol(seg, HIP_SYMBOL(g_seg), sizeof(seg)); (void)hipMemcpyFromSymbol(stages, HIP_SYMBOL(g_stages), sizeof(stages));
+    const char* kind[3] = {"layer 1 / 3 tile, first stage (epilogue parts in records 1 .. 8)", "layer 1 / 3 tile, second stage (no epilogue)",
+                           "layer 2 tile (epilogue parts in records 1 .. 8)"};
+    const int recs[4] = {1, 7, 1, 7};
+    const char* name[4] = {"record 0", "records 1 .. 7", "record 8 (wait, barrier, DMA piece 0)", "records 9 .. 15 (DMA pieces 1 .. 7)"};
+    for (int k = 0; k < 3; ++k) {
+      printf("%s: %u stages stamped\n", kind[k], stages[k]);
+      for (int i = 0; i < 4; ++i) printf("    %-40s %8.1f clocks per record\n", name[i], stages[k] ? (double)seg[k][i] / stages[k] / recs[i] : 0.0);
+    }
+  }
+#endif
   return 0;
 }
