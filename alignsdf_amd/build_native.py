@@ -29,10 +29,11 @@ TU_FLAGS = {"k1hw_kernels.hip": UNROLL_ALL, "k1s_kernels.hip": VGPR_FORM, "k1s_n
             # (the gradient form: 256 + 229 registers and no scratch this way, 256 + 256 and 8 bytes of scratch on the default)
             "k1g_kernels.hip": VGPR_FORM,
             # (the tracing form: the resource report does not ask for it - the default build has no scratch either, at 256 + 255 registers
-            # against 256 + 247 - it is built like k1_kernels.hip because its tile body is a copy of that unit's: the same epilogues read the
-            # accumulators in place)
+            # against 256 + 247 - it is built like k1_kernels.hip because its pass of the chain (csrc/sdf_mlp_chain_pass.h) is that unit's
+            # <0, 2, false> tile body: the same epilogues read the accumulators in place)
             "k1t_kernels.hip": VGPR_FORM,
-            # (the projection form: the gradient form's tile body inside a loop, built like it)
+            # (the projection form: the gradient form's pass of the chain - the same included text, the same hooks - inside a loop, built
+            # like it)
             "k1p_kernels.hip": VGPR_FORM,
             # (the reverse-mode form: 256 + 242 registers and no scratch this way.  Its last layer loop is left rolled at the default unroll
             # threshold (indexed registers, 2.5 KB of scratch); with the SLP vectorizer on, pairs of its reduction's products become

@@ -13,7 +13,9 @@
 // The value column goes through the operations of sdf_mlp_body<0, 2, false> on the same operands: its sdf is bit-identical to
 // asdf_decode_points under ASDF_MATH_F32.  (ReLU there is max(int bits, 0); here every lane selects  bits(quad lane 0) > 0 ? v : +0,
 // which for the value lane - its own quad lane 0 - is the same function of every bit pattern.)
-// A header of its own, not a template parameter of sdf_mlp_body: every other unit compiles from unchanged text.
+// A header of its own, not a template parameter of sdf_mlp_body: every other unit compiles from unchanged text.  The pass of the chain
+// itself is sdf_mlp_chain_pass.h, the one text this body, the projection and the tracing body include; with sdf_mlp_body and the forward
+// phase of sdf_mlp_vjp_body that makes three texts, and a change to the ring, the waits or the stage schedule is made in those three.
 #pragma once
 #include "k1_launch.h"
 #include "sdf_mlp_kernel.h"
@@ -98,98 +100,14 @@ __device__ __forceinline__ void sdf_mlp_grad_body(const DecodeParams& p, const G
       if (valid) { x0 = p.xyz[pi * 3 + 0]; x1 = p.xyz[pi * 3 + 1]; x2 = p.xyz[pi * 3 + 2]; }
       // the tangent columns' point is the unit vector of their coordinate
       if (tangent) { x0 = comp == 1 ? 1.0f : 0.0f; x1 = comp == 2 ? 1.0f : 0.0f; x2 = comp == 3 ? 1.0f : 0.0f; }
-      // B operands of the point-feature K-steps: lane half h supplies feature 2 s + h of K-step s
-      float bp[KP];
-      bp[0] = half ? x1 : x0;
-      bp[1] = half ? 0.0f : x2;
-      const float* sbase = sbase0;
-      asm volatile("" : "+s"(sbase));
-      auto src_of = [&](int s) -> const float* {   // s = stage index within the head + 3
-        return sbase + (size_t)(s < kStagesHead ? s : s - kStagesHead) * kStageFloats;
-      };
-
-      // ---- layer 0
-      f32x16 h0[kTilesHidden];
-#pragma unroll
-      for (int t = 0; t < kTilesHidden; ++t) {
-        f32x16 acc = load_bias16q(hc + CL::kC0 + (t * 2 + half) * 16, tangent);
-#pragma unroll
-        for (int s = 0; s < KP; ++s) acc = ASDF_MFMA(hc[CL::kA0 + (t * KP + s) * 64 + lane], bp[s], acc);
-        h0[t] = relu16q(acc);
-      }
-
-#define ASDF_STAGE(KT, Q, SLOT, ACC, HIN, SIDX, EPI) \
-  stage<KT, Q, SLOT, 0>(ACC, HIN, ring, src_of((SIDX) + 3), lds_ring_base, lane, wave, a0, a1, EPI)
-
-      // ---- layer 1: 512 -> 256; epilogue of tile t-1 rides in tile t
-      f32x16 h1[kTilesL1];
-      f32x16 acc1[2];
-#pragma unroll
-      for (int t = 0; t < kTilesL1; ++t) {
-        f32x16& acc = acc1[t & 1];
-        acc = load_bias16q(hc + CL::kB1 + (t * 2 + half) * 16, tangent);
-        auto epi = [&]() {
-          if (t == 0) return;
-          h1[t - 1] = relu16q(acc1[(t - 1) & 1]);
-        };
-        ASDF_STAGE(16, 0, 0, acc, h0, t * 4 + 0, epi);
-        ASDF_STAGE(16, 1, 1, acc, h0, t * 4 + 1, NoEpilogue());
-        ASDF_STAGE(16, 2, 2, acc, h0, t * 4 + 2, NoEpilogue());
-        ASDF_STAGE(16, 3, 3, acc, h0, t * 4 + 3, NoEpilogue());
-      }
-
-      // ---- layer 2: [h1 (256) | xyz (4)] -> 512
-      f32x16 h2[kTilesHidden];
-      f32x16 acc2[2];
-#pragma unroll
-      for (int t = 0; t < kTilesHidden; ++t) {
-        f32x16& acc = acc2[t & 1];
-        acc = load_bias16q(hc + CL::kC2 + (t * 2 + half) * 16, tangent);
-#pragma unroll
-        for (int s = 0; s < KP; ++s) acc = ASDF_MFMA(hc[CL::kA2 + (t * KP + s) * 64 + lane], bp[s], acc);
-        auto epi = [&]() {
-          if (t > 0) h2[t - 1] = relu16q(acc2[(t - 1) & 1]);
-          else h1[kTilesL1 - 1] = relu16q(acc1[(kTilesL1 - 1) & 1]);   // consumed by K-steps >= 112
-        };
-        constexpr int S0 = kStagesL1;
-        if (t & 1) {
-          ASDF_STAGE(8, 0, 2, acc, h1, S0 + t * 2 + 0, epi);
-          ASDF_STAGE(8, 1, 3, acc, h1, S0 + t * 2 + 1, NoEpilogue());
-        } else {
-          ASDF_STAGE(8, 0, 0, acc, h1, S0 + t * 2 + 0, epi);
-          ASDF_STAGE(8, 1, 1, acc, h1, S0 + t * 2 + 1, NoEpilogue());
-        }
-      }
-
-      // ---- layer 3 (512 -> 512) fused with layer 4 (dot with w4)
-      float part = 0.0f;
-      f32x16 acc3[2];
-      auto dot_w4 = [&](const f32x16 a, int t) {
-        const f32x4* w4 = reinterpret_cast<const f32x4*>(hc + CL::kW4 + (t * 2 + half) * 16);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const f32x4 w = w4[c];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) part = fmaf(relu_quad(a[c * 4 + r]), w[r], part);
-        }
-      };
-#pragma unroll
-      for (int t = 0; t < kTilesHidden; ++t) {
-        f32x16& acc = acc3[t & 1];
-        acc = load_bias16q(hc + CL::kB3 + (t * 2 + half) * 16, tangent);
-        auto epi = [&]() {
-          if (t > 0) dot_w4(acc3[(t - 1) & 1], t - 1);
-          else h2[kTilesHidden - 1] = relu16q(acc2[(kTilesHidden - 1) & 1]);   // consumed by K-steps >= 240
-        };
-        constexpr int S0 = kStagesL1 + kStagesL2;
-        ASDF_STAGE(16, 0, 0, acc, h2, S0 + t * 4 + 0, epi);
-        ASDF_STAGE(16, 1, 1, acc, h2, S0 + t * 4 + 1, NoEpilogue());
-        ASDF_STAGE(16, 2, 2, acc, h2, S0 + t * 4 + 2, NoEpilogue());
-        ASDF_STAGE(16, 3, 3, acc, h2, S0 + t * 4 + 3, NoEpilogue());
-      }
-      dot_w4(acc3[(kTilesHidden - 1) & 1], kTilesHidden - 1);
-#undef ASDF_STAGE
-      part += __shfl_xor(part, 32);
+      // one pass of the chain on the quad: bias block for the value column only, the value column's ReLU mask on all four
+#define ASDF_CHAIN_BIAS(P) load_bias16q(P, tangent)
+#define ASDF_CHAIN_RELU16(V) relu16q(V)
+#define ASDF_CHAIN_RELU(V) relu_quad(V)
+#include "sdf_mlp_chain_pass.h"
+#undef ASDF_CHAIN_BIAS
+#undef ASDF_CHAIN_RELU16
+#undef ASDF_CHAIN_RELU
       // value lane: sdf = tanh(s); tangent lane k: grad = (1 - sdf^2) d_k, d_k = its dot without the bias
       const float sdf = tanhf(part + hc[CL::kB4]);
       const float sq = __int_as_float(quad0(__float_as_int(sdf)));

@@ -208,8 +208,9 @@ __device__ __forceinline__ void pixel_prologue(const PixelParams& q, const float
 // of MLP 0, networks/model.py:134-137,161-162 / :257-259,306-307): kMaxClasses more rows of the fused last layer.
 // PA (k1pa_kernels.hip; KP == 2, SeparateDecoder, no classifier): the latent of each point is pixel-aligned - layers 0 and 2 start
 // their accumulators from pixel_gather16 for in-image points (px: the sample's PixelParams); clear = the code above, unchanged.
-// (sdf_mlp_grad_kernel.h and sdf_mlp_trace_kernel.h hold COPIES of this body's <0, 2, false> form - gradients over point lists, ray
-// tracing: a change to the ring, the waits or the stage schedule here has to be mirrored in both by hand.)
+// (Two more texts hold this body's <0, 2, false> form: sdf_mlp_chain_pass.h, the one pass that the gradient, projection and tracing
+// bodies include, and the forward phase of sdf_mlp_vjp_body.  A change to the ring, the waits or the stage schedule is made in these
+// three places.)
 template <int ABL, int KP, bool TWO_OUT, bool CLS = false, bool PA = false>
 __device__ __forceinline__ void sdf_mlp_body(const DecodeParams& p, const PixelParams* px = nullptr) {
   static_assert(!PA || (KP == 2 && !TWO_OUT && !CLS), "the pixel-aligned form is built for SeparateDecoder with xyz features");

@@ -4,9 +4,9 @@
 // The columns of an MFMA do not interact, so "the same 128 columns again" is, to the weight ring, the next tile (src_of wraps as in
 // sdf_mlp_body) and the point a column feeds may change freely between two passes of the chain.  A column holds one ray's state in
 // registers (both lane halves of a column carry the same copy: they see the same sdf bits, so they stay equal without talking).
-// One iteration = refill the free columns, vote, form p = o + t d, one pass of the chain (a COPY of sdf_mlp_body<0, 2, false>'s tile
-// body: a change to the ring, the waits or the stage schedule there has to be mirrored here by hand, as in sdf_mlp_grad_kernel.h),
-// update the state by the rule below.  The value of a column goes through the operations of sdf_mlp_body<0, 2, false> on the same
+// One iteration = refill the free columns, vote, form p = o + t d, one pass of the chain (sdf_mlp_chain_pass.h, the text the gradient
+// and projection bodies include too: sdf_mlp_body<0, 2, false>'s tile body; a change to the ring, the waits or the stage schedule is
+// made there, in sdf_mlp_body and in the forward phase of sdf_mlp_vjp_body), update the state by the rule below.  The value of a column goes through the operations of sdf_mlp_body<0, 2, false> on the same
 // operands: at every point the kernel samples, its sdf is asdf_decode_points' under ASDF_MATH_F32, bit for bit.
 //
 // The rule (all fp32, every operation rounded on its own; per ray and head; TraceRule below):
@@ -161,97 +161,14 @@ __device__ __forceinline__ void sdf_mlp_trace_body(const DecodeParams& p, const 
         x1 = __fadd_rn(o1, __fmul_rn(t, d1));
         x2 = __fadd_rn(o2, __fmul_rn(t, d2));
       }
-      float bp[KP];
-      bp[0] = half ? x1 : x0;
-      bp[1] = half ? 0.0f : x2;
-      const float* sbase = sbase0;
-      asm volatile("" : "+s"(sbase));
-      auto src_of = [&](int s) -> const float* {   // s = stage index within the head + 3
-        return sbase + (size_t)(s < kStagesHead ? s : s - kStagesHead) * kStageFloats;
-      };
-
-      // ---- layer 0
-      f32x16 h0[kTilesHidden];
-#pragma unroll
-      for (int tl = 0; tl < kTilesHidden; ++tl) {
-        f32x16 acc = load_bias16(hc + CL::kC0 + (tl * 2 + half) * 16);
-#pragma unroll
-        for (int s = 0; s < KP; ++s) acc = ASDF_MFMA(hc[CL::kA0 + (tl * KP + s) * 64 + lane], bp[s], acc);
-        h0[tl] = relu16i(acc);
-      }
-
-#define ASDF_STAGE(KT, Q, SLOT, ACC, HIN, SIDX, EPI) \
-  stage<KT, Q, SLOT, 0>(ACC, HIN, ring, src_of((SIDX) + 3), lds_ring_base, lane, wave, a0, a1, EPI)
-
-      // ---- layer 1: 512 -> 256; epilogue of tile t-1 rides in tile t
-      f32x16 h1[kTilesL1];
-      f32x16 acc1[2];
-#pragma unroll
-      for (int tl = 0; tl < kTilesL1; ++tl) {
-        f32x16& acc = acc1[tl & 1];
-        acc = load_bias16(hc + CL::kB1 + (tl * 2 + half) * 16);
-        auto epi = [&]() {
-          if (tl == 0) return;
-          h1[tl - 1] = relu16i(acc1[(tl - 1) & 1]);
-        };
-        ASDF_STAGE(16, 0, 0, acc, h0, tl * 4 + 0, epi);
-        ASDF_STAGE(16, 1, 1, acc, h0, tl * 4 + 1, NoEpilogue());
-        ASDF_STAGE(16, 2, 2, acc, h0, tl * 4 + 2, NoEpilogue());
-        ASDF_STAGE(16, 3, 3, acc, h0, tl * 4 + 3, NoEpilogue());
-      }
-
-      // ---- layer 2: [h1 (256) | xyz (4)] -> 512
-      f32x16 h2[kTilesHidden];
-      f32x16 acc2[2];
-#pragma unroll
-      for (int tl = 0; tl < kTilesHidden; ++tl) {
-        f32x16& acc = acc2[tl & 1];
-        acc = load_bias16(hc + CL::kC2 + (tl * 2 + half) * 16);
-#pragma unroll
-        for (int s = 0; s < KP; ++s) acc = ASDF_MFMA(hc[CL::kA2 + (tl * KP + s) * 64 + lane], bp[s], acc);
-        auto epi = [&]() {
-          if (tl > 0) h2[tl - 1] = relu16i(acc2[(tl - 1) & 1]);
-          else h1[kTilesL1 - 1] = relu16i(acc1[(kTilesL1 - 1) & 1]);   // consumed by K-steps >= 112
-        };
-        constexpr int S0 = kStagesL1;
-        if (tl & 1) {
-          ASDF_STAGE(8, 0, 2, acc, h1, S0 + tl * 2 + 0, epi);
-          ASDF_STAGE(8, 1, 3, acc, h1, S0 + tl * 2 + 1, NoEpilogue());
-        } else {
-          ASDF_STAGE(8, 0, 0, acc, h1, S0 + tl * 2 + 0, epi);
-          ASDF_STAGE(8, 1, 1, acc, h1, S0 + tl * 2 + 1, NoEpilogue());
-        }
-      }
-
-      // ---- layer 3 (512 -> 512) fused with layer 4 (dot with w4) and tanh
-      float part = 0.0f;
-      f32x16 acc3[2];
-      auto dot_w4 = [&](const f32x16 a, int tl) {
-        const f32x4* w4 = reinterpret_cast<const f32x4*>(hc + CL::kW4 + (tl * 2 + half) * 16);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const f32x4 w = w4[c];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) part = fmaf(__int_as_float(max(__float_as_int(a[c * 4 + r]), 0)), w[r], part);
-        }
-      };
-#pragma unroll
-      for (int tl = 0; tl < kTilesHidden; ++tl) {
-        f32x16& acc = acc3[tl & 1];
-        acc = load_bias16(hc + CL::kB3 + (tl * 2 + half) * 16);
-        auto epi = [&]() {
-          if (tl > 0) dot_w4(acc3[(tl - 1) & 1], tl - 1);
-          else h2[kTilesHidden - 1] = relu16i(acc2[(kTilesHidden - 1) & 1]);   // consumed by K-steps >= 240
-        };
-        constexpr int S0 = kStagesL1 + kStagesL2;
-        ASDF_STAGE(16, 0, 0, acc, h2, S0 + tl * 4 + 0, epi);
-        ASDF_STAGE(16, 1, 1, acc, h2, S0 + tl * 4 + 1, NoEpilogue());
-        ASDF_STAGE(16, 2, 2, acc, h2, S0 + tl * 4 + 2, NoEpilogue());
-        ASDF_STAGE(16, 3, 3, acc, h2, S0 + tl * 4 + 3, NoEpilogue());
-      }
-      dot_w4(acc3[(kTilesHidden - 1) & 1], kTilesHidden - 1);
-#undef ASDF_STAGE
-      part += __shfl_xor(part, 32);
+      // one pass of the chain: sdf_mlp_body<0, 2, false>'s bias and ReLU
+#define ASDF_CHAIN_BIAS(P) load_bias16(P)
+#define ASDF_CHAIN_RELU16(V) relu16i(V)
+#define ASDF_CHAIN_RELU(V) __int_as_float(max(__float_as_int(V), 0))
+#include "sdf_mlp_chain_pass.h"
+#undef ASDF_CHAIN_BIAS
+#undef ASDF_CHAIN_RELU16
+#undef ASDF_CHAIN_RELU
       const float f = tanhf(part + hc[CL::kB4]);
 
       // ---- the rule

@@ -10,6 +10,8 @@
 // FORWARD PHASE: a copy of sdf_mlp_body<0, 2, false> for a point list (32 points per wave, 128 per workgroup) - the same operations on
 // the same operands, so a written sdf is asdf_decode_points' under ASDF_MATH_F32 bit for bit - whose epilogues also keep the masks
 // m_l = [pre-activation > 0] as bits: a 32x32 tile is 16 bits per lane, two tiles share a register, m0 .. m3 = 8 + 4 + 8 + 8 = 28.
+// (One of the chain's three texts, with sdf_mlp_body and sdf_mlp_chain_pass.h: a change to the ring, the waits or the stage schedule
+// is made in all three.  The masks per register and the hoff addresses are why it does not include the pass fragment.)
 // REVERSE PHASE: the same stage<> machinery over a second weight image (VjpParams::streamT, packed by pack_decoder with the same
 // lambda, indices swapped): W3^T has L3's shape (16 tiles x 4 stages), W2a^T L1's (8 x 4), W1^T L2's (16 x 2), in that order; the ring
 // runs on from the forward image into it and wraps back for the next tile (256 stages per tile and head).

@@ -8,6 +8,7 @@ libalignsdf_hip.so.
 """
 import collections
 import ctypes
+import functools
 import logging
 import os
 
@@ -193,58 +194,39 @@ def pixel_align_refusal(combined, point_feat_size, encode_style, num_class):
     return None
 
 
-def grad_refusal(combined, point_feat_size, encode_style, pixel_align):
-    """Why (a string) the gradient form of the fp32 chain (HipSdfDecoder.decode_points_grad, csrc/k1g_kernels.hip) does not cover a
-    decoder of this shape, or None.  It is built for SeparateDecoder with point features that are affine in xyz: plain xyz and the
-    "hand" / "obj" / "both" kinematic embeddings - every shipped config.  A part classifier does not matter (it is not evaluated)."""
+# the forms of the fp32 chain over point lists and rays: what the sentences below call the form's kernel, and why it has no
+# pixel-aligned form
+_NOT_DIFFERENTIATED = "the bicubic gather is not differentiated"
+_CHAIN_FORMS = {"grad": ("gradient", _NOT_DIFFERENTIATED), "vjp": ("reverse-mode", _NOT_DIFFERENTIATED),
+                "trace": ("ray-tracing", "the ray-tracing kernel has no bicubic gather"), "project": ("projection", _NOT_DIFFERENTIATED)}
+
+
+def chain_refusal(form, combined, point_feat_size, encode_style, pixel_align):
+    """Why (a string) a form of the fp32 chain - "grad": HipSdfDecoder.decode_points_grad, csrc/k1g_kernels.hip; "vjp":
+    decode_points_vjp and the code fits, k1v / k1vb_kernels.hip; "trace": trace_rays, k1t_kernels.hip; "project": project_points,
+    k1p_kernels.hip - does not cover a decoder of this shape, or None.  One coverage for all of them: SeparateDecoder with point
+    features that are affine in xyz, plain xyz and the "hand" / "obj" / "both" kinematic embeddings - every shipped config.  A part
+    classifier does not matter (it is not evaluated)."""
+    kernel, no_pixel_form = _CHAIN_FORMS[form]
     if combined:
-        return "CombinedDecoder (the gradient kernel is built for SeparateDecoder)"
+        return "CombinedDecoder (the %s kernel is built for SeparateDecoder)" % kernel
     if pixel_align:
-        return "pixel-aligned latent (the bicubic gather is not differentiated)"
+        return "pixel-aligned latent (%s)" % no_pixel_form
     if encode_style == "nerf" and int(point_feat_size) > 3:
         return "NeRF encoding with PointFeatSize %d (only point features affine in xyz are built)" % int(point_feat_size)
     return None
 
 
-def vjp_refusal(combined, point_feat_size, encode_style, pixel_align):
-    """Why (a string) the reverse-mode form of the fp32 chain (HipSdfDecoder.decode_points_vjp, csrc/k1v_kernels.hip) does not cover a
-    decoder of this shape, or None.  Its coverage is the gradient kernel's: SeparateDecoder with point features affine in xyz."""
-    if combined:
-        return "CombinedDecoder (the reverse-mode kernel is built for SeparateDecoder)"
-    if pixel_align:
-        return "pixel-aligned latent (the bicubic gather is not differentiated)"
-    if encode_style == "nerf" and int(point_feat_size) > 3:
-        return "NeRF encoding with PointFeatSize %d (only point features affine in xyz are built)" % int(point_feat_size)
-    return None
+# chain_refusal of one form each: (combined, point_feat_size, encode_style, pixel_align) -> a string or None
+grad_refusal = functools.partial(chain_refusal, "grad")
+vjp_refusal = functools.partial(chain_refusal, "vjp")
+trace_refusal = functools.partial(chain_refusal, "trace")
+project_refusal = functools.partial(chain_refusal, "project")
 
 
 # what decode_points_vjp returns (HipSdfDecoder and TorchModuleDecoder): sdf_* [M] or None, d_latent [L], d_embed = (hand [pf_h, 4],
 # obj [pf_o, 4]) or None, d_fold [2, 2, 512, 4] or None
 SdfVjp = collections.namedtuple("SdfVjp", "sdf_hand sdf_obj d_latent d_embed d_fold")
-
-
-def trace_refusal(combined, point_feat_size, encode_style, pixel_align):
-    """Why (a string) the ray-tracing form of the fp32 chain (HipSdfDecoder.trace_rays, csrc/k1t_kernels.hip) does not cover a decoder
-    of this shape, or None.  Its coverage is the gradient kernel's: SeparateDecoder with point features affine in xyz."""
-    if combined:
-        return "CombinedDecoder (the ray-tracing kernel is built for SeparateDecoder)"
-    if pixel_align:
-        return "pixel-aligned latent (the ray-tracing kernel has no bicubic gather)"
-    if encode_style == "nerf" and int(point_feat_size) > 3:
-        return "NeRF encoding with PointFeatSize %d (only point features affine in xyz are built)" % int(point_feat_size)
-    return None
-
-
-def project_refusal(combined, point_feat_size, encode_style, pixel_align):
-    """Why (a string) the projection form of the fp32 chain (HipSdfDecoder.project_points, csrc/k1p_kernels.hip) does not cover a
-    decoder of this shape, or None.  Its coverage is the gradient kernel's: SeparateDecoder with point features affine in xyz."""
-    if combined:
-        return "CombinedDecoder (the projection kernel is built for SeparateDecoder)"
-    if pixel_align:
-        return "pixel-aligned latent (the bicubic gather is not differentiated)"
-    if encode_style == "nerf" and int(point_feat_size) > 3:
-        return "NeRF encoding with PointFeatSize %d (only point features affine in xyz are built)" % int(point_feat_size)
-    return None
 
 
 class HipSdfDecoder:
@@ -1340,33 +1322,71 @@ class HipSdfDecoder:
                                                      self._stream()), "asdf_decode_points")
         return hand, obj
 
+    # the methods on the point and ray forms of the fp32 chain (the library's entry is asdf_<method>): the form whose coverage they have
+    # (chain_refusal), what their messages call the kernel, the library's own refusal code and what that code may be about
+    _CHAIN_METHODS = {"decode_points_grad": ("grad", "gradient", _native.ENOGRAD, "decoder or sample"),
+                      "decode_points_vjp": ("vjp", "reverse-mode", _native.ENOGRAD, "decoder or sample"),
+                      "fit_code": ("vjp", "fit", _native.ENOGRAD, "decoder or sample"),
+                      "fit_codes": ("vjp", "fit", _native.ENOGRAD, "decoder"),
+                      "trace_rays": ("trace", "ray-tracing", _native.ENOTRACE, "decoder or sample"),
+                      "project_points": ("project", "projection", _native.ENOPROJECT, "decoder or sample")}
+
+    def _chain_gate(self, method, ask=False):
+        """The coverage rule around one of _CHAIN_METHODS.  ask=True: why the method would refuse this decoder, or None.  Else
+        NotImplementedError with that reason, or, for a decoder it covers, check(code) for the native call's return value: the
+        library's own gate is the same refusal (whatever chain_refusal missed is still a refusal, not a native error), every other
+        code goes through _native.check."""
+        form, kernel, refused, about = self._CHAIN_METHODS[method]
+        why = chain_refusal(form, self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
+        if ask:
+            return why
+        if why is not None:
+            raise NotImplementedError("the %s kernel does not cover this decoder: %s" % (kernel, why))
+
+        def check(code):
+            if code == refused:
+                raise NotImplementedError("the %s kernel does not cover this %s: %s" % (kernel, about, self._L.asdf_strerror(code).decode()))
+            _native.check(code, "asdf_" + method)
+        return check
+
     def grad_refusal(self):
-        """grad_refusal() of this decoder: why decode_points_grad would refuse, or None."""
-        return grad_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
+        """Why decode_points_grad would refuse this decoder, or None."""
+        return self._chain_gate("decode_points_grad", ask=True)
+
+    def vjp_refusal(self):
+        """Why decode_points_vjp would refuse this decoder, or None."""
+        return self._chain_gate("decode_points_vjp", ask=True)
+
+    def fit_code_refusal(self):
+        """Why fit_code would refuse this decoder, or None: the coverage of the reverse-mode kernel (vjp_refusal)."""
+        return self._chain_gate("fit_code", ask=True)
+
+    def fit_codes_refusal(self):
+        """Why fit_codes would refuse this decoder, or None: what fit_code refuses."""
+        return self._chain_gate("fit_codes", ask=True)
+
+    def trace_refusal(self):
+        """Why trace_rays would refuse this decoder, or None."""
+        return self._chain_gate("trace_rays", ask=True)
+
+    def project_refusal(self):
+        """Why project_points would refuse this decoder, or None."""
+        return self._chain_gate("project_points", ask=True)
 
     def decode_points_grad(self, xyz, hand=True, obj=True):
         """SDF and its gradient with respect to the normalised query points [M,3], in one forward-mode pass of the fp32 chain
         (csrc/k1g_kernels.hip; the math mode of the sweeps is neither read nor changed).  Returns (sdf_hand [M], grad_hand [M,3],
         sdf_obj [M], grad_obj [M,3]) device tensors, None for a head switched off.  The SDF values are decode_points' under
         set_math("f32"), bit for bit.  NotImplementedError(reason) for a decoder grad_refusal() does not cover."""
-        why = self.grad_refusal()
-        if why is not None:
-            raise NotImplementedError("the gradient kernel does not cover this decoder: %s" % why)
+        check = self._chain_gate("decode_points_grad")
         xyz = xyz.detach().to(device=self.device, dtype=torch.float32).contiguous()
         M = xyz.shape[0]
         new = lambda on, *shape: torch.empty(shape, dtype=torch.float32, device=self.device) if on else None
         sh, gh, so, go = new(hand, M), new(hand, M, 3), new(obj, M), new(obj, M, 3)
         ptr = lambda t: t.data_ptr() if t is not None else None
         with torch.cuda.device(self.device):
-            code = self._L.asdf_decode_points_grad(self._h, xyz.data_ptr(), M, ptr(sh), ptr(gh), ptr(so), ptr(go), self._stream())
-        if code == _native.ENOGRAD:        # (the library's own gate: whatever grad_refusal() missed is still a refusal, not a native error)
-            raise NotImplementedError("the gradient kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
-        _native.check(code, "asdf_decode_points_grad")
+            check(self._L.asdf_decode_points_grad(self._h, xyz.data_ptr(), M, ptr(sh), ptr(gh), ptr(so), ptr(go), self._stream()))
         return sh, gh, so, go
-
-    def vjp_refusal(self):
-        """vjp_refusal() of this decoder: why decode_points_vjp would refuse, or None."""
-        return vjp_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
 
     def decode_points_vjp(self, xyz, w_hand=None, w_obj=None, want_sdf=True):
         """Reverse mode over the normalised query points [M,3] in one launch of the fp32 chain (csrc/k1v_kernels.hip; the math mode of
@@ -1376,9 +1396,7 @@ class HipSdfDecoder:
         - device tensors, nothing waits for the device.  A head whose weights are None is not evaluated: its sdf is None, its d_embed
         and d_fold block are zero.  The SDF values are decode_points' under set_math("f32"), bit for bit; every sum is taken in a fixed
         order, so the same call twice gives the same bits.  NotImplementedError(reason) for a decoder vjp_refusal() does not cover."""
-        why = self.vjp_refusal()
-        if why is not None:
-            raise NotImplementedError("the reverse-mode kernel does not cover this decoder: %s" % why)
+        check = self._chain_gate("decode_points_vjp")
         xyz = xyz.detach().to(device=self.device, dtype=torch.float32).contiguous()
         M = xyz.shape[0]
         if xyz.dim() != 2 or xyz.shape[1] != 3:
@@ -1396,16 +1414,9 @@ class HipSdfDecoder:
         d_embed = new(True, 2, _native.MAX_POINT_FEATS, 4)
         ptr = lambda t: t.data_ptr() if t is not None else None
         with torch.cuda.device(self.device):
-            code = self._L.asdf_decode_points_vjp(self._h, xyz.data_ptr(), M, ptr(ws[0]), ptr(ws[1]), ptr(sh), ptr(so), d_fold.data_ptr(),
-                                                  d_latent.data_ptr(), d_embed.data_ptr(), self._stream())
-        if code == _native.ENOGRAD:
-            raise NotImplementedError("the reverse-mode kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
-        _native.check(code, "asdf_decode_points_vjp")
+            check(self._L.asdf_decode_points_vjp(self._h, xyz.data_ptr(), M, ptr(ws[0]), ptr(ws[1]), ptr(sh), ptr(so), d_fold.data_ptr(),
+                                                 d_latent.data_ptr(), d_embed.data_ptr(), self._stream()))
         return SdfVjp(sh, so, d_latent, (d_embed[0, :self._pf[0]], d_embed[1, :self._pf[1]]), d_fold)
-
-    def fit_code_refusal(self):
-        """Why fit_code would refuse this decoder, or None: the coverage of the reverse-mode kernel (vjp_refusal)."""
-        return vjp_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
 
     def fit_code(self, xyz, t_hand, t_obj, n_hand, n_obj, latent, z0=None, steps=800, lr=5e-3, decay=0.1, every=400, prior=1e-4,
                  clamp=0.05):
@@ -1419,9 +1430,7 @@ class HipSdfDecoder:
         is then bound to the fitted code.  The rule, operation by operation: fit.clamped_l1_rule and fit.adam_step_host - which
         fit.fit_code_lockstep runs one step at a time, to the same bits.  NotImplementedError(reason) for a decoder
         fit_code_refusal() does not cover."""
-        why = self.fit_code_refusal()
-        if why is not None:
-            raise NotImplementedError("the fit kernel does not cover this decoder: %s" % why)
+        check = self._chain_gate("fit_code")
         if self._bound is None:
             raise ValueError("fit_code: bind the sample (its point embedding) with set_sample first")
         dev32 = self._dev32
@@ -1438,18 +1447,13 @@ class HipSdfDecoder:
         table = self._fit_table(steps, lr, decay, every)
         ptr = lambda t: t.data_ptr() if t is not None else None
         with torch.cuda.device(self.device):
-            code = self._L.asdf_fit_code(self._h, xyz.data_ptr(), M, ptr(ts[0]), int(n_hand), ptr(ts[1]), int(n_obj), float(clamp),
-                                         z.data_ptr(), ptr(z0), float(prior), table.data_ptr(), steps, self._fit_state.data_ptr(),
-                                         _native.FIT_STATE_BYTES, history.data_ptr(), self._stream())
-        if code == _native.ENOGRAD:
-            raise NotImplementedError("the fit kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
-        _native.check(code, "asdf_fit_code")
+            check(self._L.asdf_fit_code(self._h, xyz.data_ptr(), M, ptr(ts[0]), int(n_hand), ptr(ts[1]), int(n_obj), float(clamp),
+                                        z.data_ptr(), ptr(z0), float(prior), table.data_ptr(), steps, self._fit_state.data_ptr(),
+                                        _native.FIT_STATE_BYTES, history.data_ptr(), self._stream()))
         if steps > 0 and M > 0:
             self._bound = (z.reshape(1, -1), self._bound[1])
             self._latent = z
         return z, history
-
-    fit_codes_refusal = fit_code_refusal      # (fit_codes refuses what fit_code refuses)
 
     def _dev32(self, t):
         return torch.as_tensor(t).detach().to(device=self.device, dtype=torch.float32).contiguous()
@@ -1494,9 +1498,7 @@ class HipSdfDecoder:
         clamp are shared.  Returns (latents [B, L], history [B, steps] fp64) as device tensors; nothing is read back and nothing
         waits.  The decoder's bound sample, math mode and status are neither needed nor changed.  NotImplementedError(reason) for a
         decoder fit_codes_refusal() does not cover."""
-        why = self.fit_codes_refusal()
-        if why is not None:
-            raise NotImplementedError("the fit kernel does not cover this decoder: %s" % why)
+        check = self._chain_gate("fit_codes")
         dev32 = self._dev32
         B, steps = len(xyz_list), int(steps)
         if B < 1:
@@ -1552,17 +1554,10 @@ class HipSdfDecoder:
         workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
         ptr = lambda t: t.data_ptr() if t is not None else None
         with torch.cuda.device(self.device):
-            code = self._L.asdf_fit_codes(self._h, B, xyz.data_ptr(), m_arr, ptr(ts[0]), ns[0], ptr(ts[1]), ns[1], float(clamp), z.data_ptr(),
-                                          ptr(z0t), emb.data_ptr(), float(prior), table.data_ptr(), steps, workspace.data_ptr(), nbytes.value,
-                                          history.data_ptr(), self._stream())
-        if code == _native.ENOGRAD:
-            raise NotImplementedError("the fit kernel does not cover this decoder: %s" % self._L.asdf_strerror(code).decode())
-        _native.check(code, "asdf_fit_codes")
+            check(self._L.asdf_fit_codes(self._h, B, xyz.data_ptr(), m_arr, ptr(ts[0]), ns[0], ptr(ts[1]), ns[1], float(clamp), z.data_ptr(),
+                                         ptr(z0t), emb.data_ptr(), float(prior), table.data_ptr(), steps, workspace.data_ptr(), nbytes.value,
+                                         history.data_ptr(), self._stream()))
         return z, history
-
-    def trace_refusal(self):
-        """trace_refusal() of this decoder: why trace_rays would refuse, or None."""
-        return trace_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
 
     def trace_rays(self, origins, dirs, t0, t1, hand=True, obj=True, max_steps=64, refine_steps=6, step_scale=1.0, min_step=1e-3,
                    max_step=0.05, want_bracket=False, want_evals=False):
@@ -1575,9 +1570,7 @@ class HipSdfDecoder:
         NotImplementedError(reason) for a decoder trace_refusal() does not cover (TorchModuleDecoder.trace_rays follows the same
         rule on the module)."""
         from .render import pack_rays
-        why = self.trace_refusal()
-        if why is not None:
-            raise NotImplementedError("the ray-tracing kernel does not cover this decoder: %s" % why)
+        check = self._chain_gate("trace_rays")
         rays = pack_rays(origins, dirs, t0, t1, self.device)
         M = rays.shape[0]
         res, args = {}, []
@@ -1594,15 +1587,8 @@ class HipSdfDecoder:
             args += [r[k].data_ptr() if r is not None and k in r else None for k in ("t", "status", "bracket", "evals")]
         params = _native.TraceParams(int(max_steps), int(refine_steps), float(step_scale), float(min_step), float(max_step))
         with torch.cuda.device(self.device):
-            code = self._L.asdf_trace_rays(self._h, rays.data_ptr(), M, ctypes.byref(params), *args, self._stream())
-        if code == _native.ENOTRACE:       # (the library's own gate: whatever trace_refusal() missed is still a refusal, not a native error)
-            raise NotImplementedError("the ray-tracing kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
-        _native.check(code, "asdf_trace_rays")
+            check(self._L.asdf_trace_rays(self._h, rays.data_ptr(), M, ctypes.byref(params), *args, self._stream()))
         return res
-
-    def project_refusal(self):
-        """project_refusal() of this decoder: why project_points would refuse, or None."""
-        return project_refusal(self.combined, self.point_feat_size, self.encode_style, getattr(self, "pixel_align", False))
 
     def project_points(self, xyz, head, max_iters=8, tol=1e-6, max_move=2.0 / 127, min_grad2=1e-12):
         """Newton projection onto the zero level of one head inside one kernel (csrc/k1p_kernels.hip; the rule: include/alignsdf_hip.h,
@@ -1613,9 +1599,7 @@ class HipSdfDecoder:
         decode_points_grad's, bit for bit; the math mode of the sweeps is neither read nor changed.  NotImplementedError(reason) for a
         decoder project_refusal() does not cover (TorchModuleDecoder.project_points follows the same rule on the module)."""
         from .project import check_rule, head_index
-        why = self.project_refusal()
-        if why is not None:
-            raise NotImplementedError("the projection kernel does not cover this decoder: %s" % why)
+        check = self._chain_gate("project_points")
         h = head_index(head)
         check_rule(max_iters, tol, max_move, min_grad2)
         xyz = xyz.detach().to(device=self.device, dtype=torch.float32).reshape(-1, 3).contiguous()
@@ -1625,11 +1609,8 @@ class HipSdfDecoder:
                "sdf_in": new(torch.float32, M), "status": new(torch.int32, M), "evals": new(torch.int32, M)}
         params = _native.ProjectParams(int(max_iters), float(tol), float(max_move), float(min_grad2))
         with torch.cuda.device(self.device):
-            code = self._L.asdf_project_points(self._h, xyz.data_ptr(), M, h, ctypes.byref(params),
-                                               *[t.data_ptr() for t in res.values()], self._stream())
-        if code == _native.ENOPROJECT:     # (the library's own gate: whatever project_refusal() missed is still a refusal, not a native error)
-            raise NotImplementedError("the projection kernel does not cover this decoder or sample: %s" % self._L.asdf_strerror(code).decode())
-        _native.check(code, "asdf_project_points")
+            check(self._L.asdf_project_points(self._h, xyz.data_ptr(), M, h, ctypes.byref(params),
+                                              *[t.data_ptr() for t in res.values()], self._stream()))
         return res
 
     def classify_points(self, xyz, want_sdf=True):

@@ -73,6 +73,37 @@ def test_grad_refusal():
     assert isinstance(grad_refusal(False, 3, "nerf", True), str)          # pixel-aligned
 
 
+NOT_DIFFERENTIATED = "pixel-aligned latent (the bicubic gather is not differentiated)"
+NERF9 = "NeRF encoding with PointFeatSize 9 (only point features affine in xyz are built)"
+NERF15 = "NeRF encoding with PointFeatSize 15 (only point features affine in xyz are built)"
+# (combined, 3, "nerf", no pixel), (separate, 3, "nerf", pixel), (separate, 9, "nerf", no pixel), (separate, 15, "nerf", no pixel)
+REFUSAL_SENTENCES = {
+    "grad_refusal": ("CombinedDecoder (the gradient kernel is built for SeparateDecoder)", NOT_DIFFERENTIATED, NERF9, NERF15),
+    "vjp_refusal": ("CombinedDecoder (the reverse-mode kernel is built for SeparateDecoder)", NOT_DIFFERENTIATED, NERF9, NERF15),
+    "trace_refusal": ("CombinedDecoder (the ray-tracing kernel is built for SeparateDecoder)",
+                      "pixel-aligned latent (the ray-tracing kernel has no bicubic gather)", NERF9, NERF15),
+    "project_refusal": ("CombinedDecoder (the projection kernel is built for SeparateDecoder)", NOT_DIFFERENTIATED, NERF9, NERF15),
+}
+
+
+@pytest.mark.parametrize("name", sorted(REFUSAL_SENTENCES))
+def test_every_refusal_sentence_is_pinned(name):
+    """The four coverage rules of the fp32 chain's point and ray forms, sentence by sentence: callers show them to the user
+    (NotImplementedError) and tests look for words in them."""
+    from alignsdf_amd import hip_decoder
+    refusal = getattr(hip_decoder, name)
+    combined, pixel, nerf9, nerf15 = REFUSAL_SENTENCES[name]
+    assert refusal(True, 3, "nerf", False) == combined
+    assert refusal(False, 3, "nerf", True) == pixel
+    assert refusal(False, 9, "nerf", False) == nerf9
+    assert refusal(False, 15, "nerf", False) == nerf15
+    assert refusal(False, 3, "nerf", False) is None
+    for size in (3, 6, 9, 15):
+        assert refusal(False, size, "both", False) is None
+    # (the signature: the same four names, by keyword as by position)
+    assert refusal(combined=True, point_feat_size=3, encode_style="nerf", pixel_align=False) == combined
+
+
 TWO_TRIANGLES = (np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0.5]], np.float32), np.array([[0, 1, 2], [2, 1, 3]]))
 # what write_ply wrote for them before it knew normals
 TWO_TRIANGLES_FILE = (

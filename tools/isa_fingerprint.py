@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel fingerprint of the decoder translation units' device code, for refactors that must not change it.
 
-Each unit is compiled to device-only assembly with the shipped flags (the command line of tests/test_kernel_resources.py:
--S --cuda-device-only plus build_native.TU_FLAGS).  Every kernel (.amdhsa_kernel NAME) is cut from its label to its last
+Each unit is compiled to device-only assembly with the shipped flags (-S --cuda-device-only plus build_native's FLAGS and
+TU_FLAGS: the build's own lists, so the tool cannot drift from it).  Every kernel (.amdhsa_kernel NAME) is cut from its label to its last
 s_endpgm and hashed.  Two compiles of the same source differ only in the __hip_cuid_* symbol at the end of the file, so the
 cut text is reproducible.  Comments are dropped, and so is the function number the compiler puts into local labels
 (.LBB<f>_<b>): both only say where in the file the function stands.
@@ -22,10 +22,12 @@ import tempfile
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
-from alignsdf_amd.build_native import HIPCC, TU_FLAGS      # noqa: E402
+from alignsdf_amd.build_native import FLAGS, HIPCC, TU_FLAGS     # noqa: E402
 
+# the sweep units and every unit that carries the fp32 chain (gradient, projection, tracing, reverse mode and its batched loss form)
 UNITS = ["decoder.hip", "k1_kernels.hip", "k1pa_kernels.hip", "k1_cls_kernels.hip", "k1h_kernels.hip", "k1hw_kernels.hip",
-         "k1h_nerf_kernels.hip", "k1s_kernels.hip", "k1s_nerf_kernels.hip"]
+         "k1h_nerf_kernels.hip", "k1s_kernels.hip", "k1s_nerf_kernels.hip",
+         "k1g_kernels.hip", "k1p_kernels.hip", "k1t_kernels.hip", "k1v_kernels.hip", "k1vb_kernels.hip"]
 
 
 def cut_kernels(isa):
@@ -46,8 +48,7 @@ def fingerprint(csrc, asm_dir=None):
     table = {}
     with tempfile.TemporaryDirectory() as tmp:
         tmp = asm_dir or tmp
-        procs = [(u, subprocess.Popen([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", *TU_FLAGS.get(u, []),
-                                       "-S", "--cuda-device-only", u, "-o", os.path.join(tmp, u + ".s")], cwd=csrc, stderr=subprocess.PIPE, text=True))
+        procs = [(u, subprocess.Popen([HIPCC, *FLAGS, *TU_FLAGS.get(u, []), "-S", "--cuda-device-only", u, "-o", os.path.join(tmp, u + ".s")], cwd=csrc, stderr=subprocess.PIPE, text=True))
                  for u in UNITS]
         for u, proc in procs:
             _, err = proc.communicate()
